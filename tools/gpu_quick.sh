@@ -12,7 +12,7 @@ if [ -n "$TESTS" ]; then
 fi
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { echo smoke failed; cat $OUT/smoke.log; exit 1; }
 cat $OUT/smoke.log
-timeout -k 10 400 python bench.py "$@" > $OUT/bench.json 2> $OUT/bench.err || { echo bench failed; tail -30 $OUT/bench.err; exit 1; }
+timeout -k 10 400 python bench.py --full "$@" > $OUT/bench.json 2> $OUT/bench.err || { echo bench failed; tail -30 $OUT/bench.err; exit 1; }
 cat $OUT/bench.json
 if [ -n "$KB" ]; then
   timeout -k 10 300 python tools/kbench.py $KB > $OUT/kbench.txt 2>&1 || { echo kbench failed; tail -30 $OUT/kbench.txt; exit 1; }

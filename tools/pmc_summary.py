@@ -1,12 +1,13 @@
-"""Per-kernel HBM traffic of the last train step from bench.py's PMC child
-passes (gpurun_out/bench_pmc/{fetch_size,write_size}) -> CSV on stdout.
+"""Per-kernel HBM traffic of the last train step from the PMC child passes of
+`bench.py --full --pmc-dir DIR` (DIR/bench_pmc/{fetch_size,write_size}; give
+DIR/bench_pmc as the argument) -> CSV on stdout.
 FETCH_SIZE / WRITE_SIZE are KiB as rocprofv3 reports them (apply the gfx950
 x2 FETCH_SIZE correction when comparing with byte counts)."""
 import csv
 import glob
 import sys
 
-root = sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/bench_pmc"
+root = sys.argv[1] if len(sys.argv) > 1 else "bench_pmc"
 print("counter,kernel,dispatches,total_kib_last_step")
 for c in ("fetch_size", "write_size"):
     f = glob.glob(f"{root}/{c}/**/*counter_collection.csv", recursive=True)[0]
