@@ -90,6 +90,13 @@ typedef struct seg_epilogue {
  * 1=VALID).  Mirrors tf.nn.conv2d's shape function (Network/model/FCN.py:130). */
 int seg_conv_desc_init(seg_conv_desc* d, int N, int H, int W, int C, int K, int R, int S,
                        int stride, int dilation, int padding, int dtype);
+/* The same with a stride and a dilation per axis (tf.nn.conv2d's
+ * strides=[1,sh,sw,1], dilations=[1,dh,dw,1]: Network/model/LidCamNet.py:45-53,
+ * Network/utils/utils.py:182); the SAME / VALID rule is applied per axis.
+ * seg_conv_desc_init(.., s, d, ..) fills the bytes of
+ * seg_conv_desc_init2(.., s, s, d, d, ..). */
+int seg_conv_desc_init2(seg_conv_desc* d, int N, int H, int W, int C, int K, int R, int S,
+                        int stride_h, int stride_w, int dil_h, int dil_w, int padding, int dtype);
 /* Fill a conv2d_transpose descriptor from the requested output shape; fails
  * with SEG_ESHAPE unless ceil(out/stride) == in (SAME) -- TF's rule
  * (Network/model/FCN.py:155, :106). */
@@ -233,8 +240,24 @@ int seg_bn_grad_finish_batch(const seg_bn_finish_segment* dev_segs, int nsegs, i
                              void* stream);
 int seg_conv2d_bwd_data_bn(const seg_conv_desc* d, const void* dy, const void* w_hwio, const seg_bn_bwd* bn,
                            void* dx, void* ws, size_t ws_bytes, void* stream);
+/* Conv2DBackpropInput.  Stride 1: any filter / dilation.  Stride > 1 (the
+ * 4x4 / 2 encoder convs of Network/model/LidCamNet.py:34-38) only with
+ * dil_h == dil_w == 1, R % stride_h == 0 and S % stride_w == 0 (the phase
+ * split's condition, as seg_tconv2d_fwd); anything else -- 3x3 / 2, stride
+ * with dilation -- returns SEG_EINVAL and writes nothing.  The strided form
+ * needs no workspace, reads the same HWIO copy, takes the same epilogue
+ * (residual, in place included; relu_mask + mask_scale) and channel-slice
+ * views (ldx > C, ldy > K), and writes the padding channels of dx as zeros.
+ * It runs dgrad_s2 (one dy halo per tile, csrc/dgrad_s2.hip) where
+ * seg_conv2d_bwd_data_s2_ok says so and the "dgrad_s2" option is 1, else the
+ * sub-pixel phase GEMMs of seg_tconv2d_fwd (bit-identical to it on the
+ * mirrored descriptor). */
 int seg_conv2d_bwd_data(const seg_conv_desc* d, const void* dy, const void* w_hwio,
                         const seg_epilogue* epi, void* dx, void* ws, size_t ws_bytes, void* stream);
+/* Whether dgrad_s2 takes this descriptor: 16-bit dtype, 4x4 filter, stride 2,
+ * no dilation, K % 32 == 0, K <= 256, C == 16 or C % 32 == 0 (padded
+ * counts).  Host-only. */
+int seg_conv2d_bwd_data_s2_ok(const seg_conv_desc* d);
 /* The ReluGrad mask as bits (round 6).  seg_conv2d_fwd_relu_bits = seg_conv2d_fwd
  * that also writes the ReLU mask of the stored y: bit k & 7 of
  * bits[pixel * ld_bits + k / 8] = (y[pixel][k] > 0), pixels dense over the

@@ -22,7 +22,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libsegkern.so")
 # MFMA / no stores -- garbage results) exist only in this separate library;
 # SEG_DIAG_LIB=1 loads it instead of the product library
 DIAG_LIB_PATH = os.path.join(PKG_DIR, "build_diag", "libsegkern_diag.so")
-SOURCES = ["igemm.hip", "igemm2.hip", "igemm3.hip", "halo.hip", "halo4.hip", "wgrad.hip", "conv.hip", "eltwise.hip", "optim.hip", "smallc.hip", "augment.hip", "dense1x1.hip"]
+SOURCES = ["igemm.hip", "igemm2.hip", "igemm3.hip", "halo.hip", "halo4.hip", "dgrad_s2.hip", "wgrad.hip", "conv.hip", "eltwise.hip", "optim.hip", "smallc.hip", "augment.hip", "dense1x1.hip"]
 HOST_SOURCES = ["pngdec.cpp", "crc32c.cpp"]
 HIP_HOST_SOURCES = ["timing.cpp"]   # host code against the HIP runtime API (hipcc, no kernels)
 HOST_LIBS = ["-lz"]
@@ -140,6 +140,7 @@ _EP = ctypes.POINTER(SegEpilogue)
 # symbol -> (restype, argtypes); must match include/segkern.h exactly
 SIGNATURES = {
     "seg_conv_desc_init": (_I, [_DP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I]),
+    "seg_conv_desc_init2": (_I, [_DP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I]),
     "seg_tconv_desc_init": (_I, [_DP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I]),
     "seg_conv2d_fwd": (_I, [_DP, _P, _P, _EP, _P, _P, _Z, _P]),
     "seg_conv2d_fwd_hwio_ok": (_I, [_DP]),
@@ -147,6 +148,7 @@ SIGNATURES = {
     "seg_conv2d_fwd_pool_ok": (_I, [_DP]),
     "seg_conv2d_fwd_pool": (_I, [_DP, _P, _P, _EP, _P, _I, _P, _I, _P, _Z, _P]),
     "seg_conv2d_bwd_data": (_I, [_DP, _P, _P, _EP, _P, _P, _Z, _P]),
+    "seg_conv2d_bwd_data_s2_ok": (_I, [_DP]),
     "seg_conv2d_fwd_relu_bits_ok": (_I, [_DP]),
     "seg_conv2d_fwd_relu_bits": (_I, [_DP, _P, _P, _EP, _P, _P, _I, _P]),
     "seg_conv2d_bwd_data_bits_ok": (_I, [_DP]),

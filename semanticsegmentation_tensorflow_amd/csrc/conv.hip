@@ -26,6 +26,7 @@ static int same_pads(int in, int k, int s, int d, int* out, int* pb, int* pa) {
 
 static int valid_out(int in, int k, int s, int d) {
     const int keff = k + (k - 1) * (d - 1);
+    if (in < keff) return 0;    // (C division truncates toward zero: -1 / 2 + 1 would be 1)
     return (in - keff) / s + 1;
 }
 
@@ -39,28 +40,35 @@ static int check_desc(const seg_conv_desc* d) {
     return SEG_OK;
 }
 
-extern "C" int seg_conv_desc_init(seg_conv_desc* d, int N, int H, int W, int C, int K, int R, int S,
-                                  int stride, int dilation, int padding, int dtype) {
-    if (!d || stride <= 0 || dilation <= 0 || N <= 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0) return SEG_EINVAL;
+extern "C" int seg_conv_desc_init2(seg_conv_desc* d, int N, int H, int W, int C, int K, int R, int S,
+                                   int stride_h, int stride_w, int dil_h, int dil_w, int padding, int dtype) {
+    if (!d || stride_h <= 0 || stride_w <= 0 || dil_h <= 0 || dil_w <= 0 || N <= 0 || H <= 0 || W <= 0 || C <= 0 ||
+        K <= 0)
+        return SEG_EINVAL;
     seg_conv_desc z = {};
     z.N = N; z.H = H; z.W = W;
     z.C = round8(C); z.K = round8(K);
     z.c_valid = C; z.k_valid = K;
     z.R = R; z.S = S;
-    z.stride_h = z.stride_w = stride;
-    z.dil_h = z.dil_w = dilation;
+    z.stride_h = stride_h; z.stride_w = stride_w;
+    z.dil_h = dil_h; z.dil_w = dil_w;
     if (padding == 0) {
-        same_pads(H, R, stride, dilation, &z.OH, &z.pad_top, &z.pad_bottom);
-        same_pads(W, S, stride, dilation, &z.OW, &z.pad_left, &z.pad_right);
+        same_pads(H, R, stride_h, dil_h, &z.OH, &z.pad_top, &z.pad_bottom);
+        same_pads(W, S, stride_w, dil_w, &z.OW, &z.pad_left, &z.pad_right);
     } else {
-        z.OH = valid_out(H, R, stride, dilation);
-        z.OW = valid_out(W, S, stride, dilation);
+        z.OH = valid_out(H, R, stride_h, dil_h);
+        z.OW = valid_out(W, S, stride_w, dil_w);
         if (z.OH <= 0 || z.OW <= 0) return SEG_ESHAPE;
     }
     z.ldx = z.C; z.ldy = z.K;
     z.dtype = dtype;
     *d = z;
     return SEG_OK;
+}
+
+extern "C" int seg_conv_desc_init(seg_conv_desc* d, int N, int H, int W, int C, int K, int R, int S,
+                                  int stride, int dilation, int padding, int dtype) {
+    return seg_conv_desc_init2(d, N, H, W, C, K, R, S, stride, stride, dilation, dilation, padding, dtype);
 }
 
 extern "C" int seg_tconv_desc_init(seg_conv_desc* d, int N, int H, int W, int C, int OH, int OW, int K,
@@ -163,6 +171,35 @@ static NTParams tconv_fwd_params(const seg_conv_desc* d) {
     p.phase = 1; p.st_h = sh; p.st_w = sw; p.pad_t = d->pad_top; p.pad_l = d->pad_left; p.Nimg = d->N;
     p.M = d->N * ((d->OH + sh - 1) / sh) * ((d->OW + sw - 1) / sw);   // max over phases
     p.Ha = (d->OH + sh - 1) / sh; p.Wa = (d->OW + sw - 1) / sw;
+    return p;
+}
+
+// Conv2DBackpropInput of a strided conv = conv2d_transpose(dy, W, input
+// shape): what the entry accepts, which route runs, and the phase-split GEMM
+// parameters of the fallback (tconv_fwd_params on the mirrored descriptor,
+// reading the conv's own HWIO copy [r][s][c][k]).
+static bool bwd_data_strided(const seg_conv_desc* d) { return d->stride_h != 1 || d->stride_w != 1; }
+
+static bool bwd_data_strided_ok(const seg_conv_desc* d) {
+    return d->dil_h == 1 && d->dil_w == 1 && d->R % d->stride_h == 0 && d->S % d->stride_w == 0;
+}
+
+static bool bwd_data_s2_shape(const seg_conv_desc* d) {
+    return (d->dtype == SEG_BF16 || d->dtype == SEG_F16) && seg::dgrad_s2_shape_ok(d);
+}
+
+// the epilogue forms dgrad_s2 has: residual and the ReluGrad mask
+static bool bwd_data_s2_runs(const seg_conv_desc* d, const seg_epilogue* e) {
+    if (!g_dgrad_s2 || !bwd_data_s2_shape(d)) return false;
+    return !e || (!e->bias && !e->scale && !e->shift && !e->relu && !(e->keep_prob > 0.f && e->keep_prob < 1.f));
+}
+
+static NTParams bwd_data_strided_params(const seg_conv_desc* d) {
+    seg_conv_desc m = *d;
+    m.H = d->OH; m.W = d->OW; m.C = d->K; m.ldx = d->ldy; m.c_valid = d->k_valid;
+    m.OH = d->H; m.OW = d->W; m.K = d->C; m.ldy = d->ldx; m.k_valid = d->c_valid;
+    NTParams p = tconv_fwd_params(&m);
+    p.w_col = d->K + g_wpad; p.w_tap = (long)d->C * (d->K + g_wpad);
     return p;
 }
 
@@ -347,7 +384,11 @@ extern "C" size_t seg_conv_workspace(const seg_conv_desc* d, int op) {
     if (check_desc(d) != SEG_OK) return 0;
     switch (op) {
         case 0: { NTParams p = conv_fwd_params(d); return seg::nt_workspace(p.M, p.N, p.K, d->dtype, 0); }
-        case 1: { NTParams p = conv_bwd_data_params(d); return seg::nt_workspace(p.M, p.N, p.K, d->dtype, 0); }
+        case 1: {
+            if (bwd_data_strided(d)) return 0;     // dgrad_s2 / the phase GEMMs: no split-K
+            NTParams p = conv_bwd_data_params(d);
+            return seg::nt_workspace(p.M, p.N, p.K, d->dtype, 0);
+        }
         case 2: {
             TNParams p = conv_bwd_filter_params(d);
             size_t need = seg::tn_workspace(p.M, p.N, p.P, d->dtype);
@@ -401,9 +442,20 @@ extern "C" int seg_conv_kernel_info(const seg_conv_desc* d, int op, char* name, 
     switch (op) {
         case 0:
         case 1: {
+            macs = macs_conv;
+            if (op == 1 && bwd_data_strided(d)) {
+                if (!bwd_data_strided_ok(d)) return SEG_EINVAL;
+                if (bwd_data_s2_runs(d, nullptr)) {
+                    fam = "dgrad_s2"; bm = 256; bn = d->C >= 32 ? 32 : 16; sp = 1;
+                    break;
+                }
+                NTParams p = bwd_data_strided_params(d);
+                p.epi.n_valid = d->c_valid; p.epi.keep_prob = 1.f;
+                fam = seg::nt_choice(p, d->dtype, d->stride_h * d->stride_w, p.M, &bm, &bn, &sp);
+                break;
+            }
             NTParams p = op == 0 ? conv_fwd_params(d) : conv_bwd_data_params(d);
             p.epi.keep_prob = 1.f;
-            macs = macs_conv;
             if (op == 0 && d->dil_w == d->dil_h && seg::smallc_fwd_ok(p, d->dtype, d->R, d->S, d->dil_h)) {
                 fam = "conv_c8"; bm = 512; bn = d->K; sp = 1;
                 break;
@@ -562,6 +614,7 @@ const Knob* find_knob(const char* name) {
         {"smallc", &seg::KnobSet::smallc, 0, 1, 1, {}},
         {"smallk", &seg::KnobSet::smallk, 0, 1, 1, {}},
         {"wpad", &seg::KnobSet::wpad, 0, 256, 8, {}},
+        {"dgrad_s2", &seg::KnobSet::dgrad_s2, 0, 1, 1, {}},   // strided input gradient: 0 = phase GEMMs only
 #ifdef SEG_DIAG
         {"tn3_abl", &seg::KnobSet::tn3_abl, 0, 3, 1, {}},
         {"smallk_abl", &seg::KnobSet::smallk_abl, 0, 3, 1, {}},
@@ -847,7 +900,16 @@ extern "C" int seg_conv2d_bwd_data(const seg_conv_desc* d, const void* dy, const
     int st = check_desc(d);
     if (st) return st;
     if (!dy || !w || !dx) return SEG_EINVAL;
-    if (d->stride_h != 1 || d->stride_w != 1) return SEG_EINVAL;  // FCN / FC-DenseNet convs are stride 1
+    if (bwd_data_strided(d)) {
+        if (!bwd_data_strided_ok(d)) return SEG_EINVAL;
+        if (bwd_data_s2_runs(d, epi)) return seg::launch_dgrad_s2(d, dy, w, epi, dx, g_wpad, (hipStream_t)stream);
+        NTParams p = bwd_data_strided_params(d);
+        p.x = dy; p.w = w; p.y = dx;
+        const int ldr = epi && epi->ld_residual ? epi->ld_residual : d->ldx;
+        p.epi = make_epi(epi, d->c_valid, (long)d->H * d->W * ldr, (long)d->H * d->W, d->ldx);
+        if (epi && epi->residual) p.epi.ld_res = ldr;
+        return seg::launch_nt(p, d->dtype, d->stride_h * d->stride_w, p.M, ws, ws_bytes, (hipStream_t)stream);
+    }
     NTParams p = conv_bwd_data_params(d);
     p.x = dy; p.w = w; p.y = dx;
     if (epi) {
@@ -856,6 +918,10 @@ extern "C" int seg_conv2d_bwd_data(const seg_conv_desc* d, const void* dy, const
         if (epi->residual && epi->ld_residual == 0) p.epi.ld_res = d->ldx;
     }
     return seg::launch_nt(p, d->dtype, 1, p.M, ws, ws_bytes, (hipStream_t)stream);
+}
+
+extern "C" int seg_conv2d_bwd_data_s2_ok(const seg_conv_desc* d) {
+    return d && check_desc(d) == SEG_OK && bwd_data_s2_shape(d) ? 1 : 0;
 }
 
 // Conv2DBackpropInput with the ReluGrad mask given as seg_conv2d_fwd_relu_bits'

@@ -358,6 +358,10 @@ int halo_kernel(const NTParams& p, const HaloPlan& hp, int dtype);
 bool halo_unpools(const HaloPlan& hp, int kernel);
 bool halo_pools(const HaloPlan& hp, int kernel);
 int launch_halo(NTParams& p, const HaloPlan& hp, int kernel, hipStream_t s, int dtype = SEG_BF16);
+// dgrad_s2.hip: Conv2DBackpropInput of a 4x4 stride-2 conv from one dy halo per tile
+bool dgrad_s2_shape_ok(const seg_conv_desc* d);
+int launch_dgrad_s2(const seg_conv_desc* d, const void* dy, const void* w_hwio, const seg_epilogue* epi, void* dx,
+                    int wpad, hipStream_t s);
 // the launch plan for p writes EpiParams.y2 (seg_conv2d_fwd_bn2)
 bool nt_bn2_ok(const NTParams& p, int dtype);
 bool res16c_ok(const NTParams& p, int dtype);

@@ -62,7 +62,8 @@ namespace seg {
     X(wgrad_abl, 0) \
     X(wgrad_nt32, 1) \
     X(wgrad_fill, 88) \
-    X(wgrad_nbias, 1)
+    X(wgrad_nbias, 1) \
+    X(dgrad_s2, 1)
 
 struct KnobSet {
 #define SEG_KNOB_MEMBER(n, d) std::atomic<int> n{d};
@@ -123,3 +124,4 @@ KnobSet& knobs();
 #define g_wgrad_nt32 (::seg::knobs().wgrad_nt32.load(std::memory_order_relaxed))   // 32-wide dy tiles for N <= 32
 #define g_wgrad_fill (::seg::knobs().wgrad_fill.load(std::memory_order_relaxed))   // split-K target: blocks = this percentage of the CUs (round 6: 88 -- in the overlapped step the side-stream filter gradients share the CUs with the input-gradient chain; 596.5 / 596.8 vs 591.5 / 591.9 img/s at 100 on one box)
 #define g_wgrad_nbias (::seg::knobs().wgrad_nbias.load(std::memory_order_relaxed))   // max channel blocks sharing the fused BiasAddGrad (1 measured best: the per-wave spread suffices)
+#define g_dgrad_s2 (::seg::knobs().dgrad_s2.load(std::memory_order_relaxed))   // strided Conv2DBackpropInput 4x4 / 2: 1 = dgrad_s2 (one dy halo per tile), 0 = the sub-pixel phase GEMMs

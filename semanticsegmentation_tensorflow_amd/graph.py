@@ -351,13 +351,30 @@ def _strides(s):
     return s[0], s[1]
 
 
+def _dilations(d):
+    if isinstance(d, int):
+        return d, d
+    d = list(d)
+    if len(d) == 4:
+        if d[0] != 1 or d[3] != 1:      # TF: "dilations in the batch and depth dimensions must be 1"
+            raise ValueError(f"dilations {d}: the batch and depth entries must be 1")
+        return int(d[1]), int(d[2])
+    return int(d[0]), int(d[1])
+
+
 def conv2d(input, filter, strides=(1, 1, 1, 1), padding="SAME", dilations=1, name=None):
+    """tf.nn.conv2d; dilations an int, [dh, dw] or [1, dh, dw, 1] (per axis:
+    Network/model/LidCamNet.py:45-53)."""
     sh, sw = _strides(strides)
-    dh, dw = _strides(dilations) if not isinstance(dilations, int) else (dilations, dilations)
-    if sh != sw or dh != dw:
-        raise NotImplementedError("anisotropic stride/dilation")
+    dh, dw = _dilations(dilations)
+    if sh != sw:
+        raise NotImplementedError("anisotropic stride")
+    if sh > 1 and (dh > 1 or dw > 1):
+        raise NotImplementedError("stride > 1 together with dilation > 1")
     R, S, C, K = filter.shape
-    op = Op("Conv2D", [input, filter], {"stride": sh, "dilation": dh, "padding": padding}, name)
+    # "dilation" stays the int the isotropic convs always had; the pair is "dilation_hw"
+    op = Op("Conv2D", [input, filter], {"stride": sh, "dilation": dh if dh == dw else (dh, dw),
+                                        "dilation_hw": (dh, dw), "padding": padding}, name)
     y = op.outputs[0]
     N, H, W, _ = input.shape
     y.shape = (N, _pads(H, R, sh, dh, padding), _pads(W, S, sw, dw, padding), K)

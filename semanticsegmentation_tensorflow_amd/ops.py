@@ -99,10 +99,21 @@ class TimingEvent:
             self._h = None
 
 
+def _hw(v):
+    return (int(v), int(v)) if isinstance(v, int) else (int(v[0]), int(v[1]))
+
+
 def conv_desc(N, H, W, C, K, R, S, stride=1, dilation=1, padding="SAME", dtype=BF16):
+    """Conv2D descriptor; stride and dilation are an int or an (h, w) pair
+    (seg_conv_desc_init2 when an axis differs)."""
     d = SegConvDesc()
-    check(_lib.lib().seg_conv_desc_init(ctypes.byref(d), N, H, W, C, K, R, S, stride, dilation,
-                                        SAME if padding == "SAME" else VALID, dtype), "conv2d")
+    (sh, sw), (dh, dw) = _hw(stride), _hw(dilation)
+    pad = SAME if padding == "SAME" else VALID
+    if sh == sw and dh == dw:
+        check(_lib.lib().seg_conv_desc_init(ctypes.byref(d), N, H, W, C, K, R, S, sh, dh, pad, dtype), "conv2d")
+    else:
+        check(_lib.lib().seg_conv_desc_init2(ctypes.byref(d), N, H, W, C, K, R, S, sh, sw, dh, dw, pad, dtype),
+              "conv2d")
     return d
 
 
@@ -357,6 +368,12 @@ def conv2d_bwd_data(desc, dy, w_hwio, dx, ws=None, stream=None, epi=None):
                                          None if epi is None else ctypes.byref(epi), ptr(dx), wsp, wss,
                                          stream_ptr(stream)), "conv2d_backprop_input")
     return dx
+
+
+def conv2d_bwd_data_s2_ok(desc):
+    """Whether dgrad_s2 (the halo kernel of the 4x4 stride-2 input gradient)
+    takes this conv; the "dgrad_s2" option set to 0 keeps it on the phase GEMMs."""
+    return bool(_lib.lib().seg_conv2d_bwd_data_s2_ok(ctypes.byref(desc)))
 
 
 def conv2d_fwd_relu_bits_ok(desc):

@@ -97,7 +97,7 @@ class PlanMixin:
             R, S, Ci, K = ins[1]
             if Ci != C:
                 raise ValueError(f"{op.name}: input depth {C} != filter depth {Ci}")
-            d = ops.conv_desc(N, H, W, C, K, R, S, op.attrs["stride"], op.attrs["dilation"],
+            d = ops.conv_desc(N, H, W, C, K, R, S, op.attrs["stride"], op.attrs["dilation_hw"],
                               op.attrs["padding"], self.cdt)
             return (N, d.OH, d.OW, K)
         if t == "Conv2DTranspose":
@@ -304,7 +304,7 @@ class PlanMixin:
                 x = n.inputs[0]
                 N, H, W, C = shp[id(x)]
                 R, S, _, K = n.w.shape
-                n.desc = ops.conv_desc(N, H, W, C, K, R, S, n.stride, n.dilation, n.padding, self.cdt)
+                n.desc = ops.conv_desc(N, H, W, C, K, R, S, n.stride, n.dilation_hw, n.padding, self.cdt)
                 ws_need = max(ws_need, ops.conv_workspace(n.desc, ops.OP_FWD))
                 # a large filter (FCN conv6 / conv7) keeps ONE packed copy: its
                 # forward reads the HWIO copy the input gradient reads

@@ -471,7 +471,7 @@ class Session(PlanMixin, StreamMixin):
                     absorbed.add(c.id)
                 nodes.append(_Node("conv", chain, [x], cur, w=w, bias=bias, relu=bool(relu), kp=kp,
                                    stride=op.attrs["stride"], dilation=op.attrs["dilation"],
-                                   padding=op.attrs["padding"]))
+                                   dilation_hw=op.attrs["dilation_hw"], padding=op.attrs["padding"]))
             elif t == "Conv2DTranspose":
                 x, w = op.inputs
                 chain = [op]
@@ -1232,7 +1232,8 @@ class Session(PlanMixin, StreamMixin):
                                          # the dgrad epilogue (igemm_nt2_bn / conv_res16c_bn)
                                          "bn_bwd": bnb,
                                          "fused_adam": False, "desc": n.desc,
-                                         "stride": n.stride, "dilation": n.dilation, "padding": n.padding})
+                                         "stride": n.stride, "dilation": n.dilation, "dilation_hw": n.dilation_hw,
+                                         "padding": n.padding})
                 want_w = n.w.var_name in p.var_set
                 want_b = n.bias is not None and n.bias.var_name in p.var_set
                 gw = store.grad(n.w.var_name) if want_w else self._scratch_grad(p, n.w)
