@@ -521,7 +521,8 @@ int seg_softmax_xent_soft_fwd_bwd(const void* logits, int ld, const float* label
 int seg_softmax(const void* x, int ldx, int C, long P, void* y, int ldy, int dtype, void* stream);
 /* pred[p] = argmax_c logits[p, c] (ties -> lowest index). */
 int seg_argmax(const void* logits, int ld, int C, long P, int64_t* pred, int dtype, void* stream);
-/* Confusion matrix counts conf[t*C+p] += 1 over the valid region (mIoU). */
+/* Confusion matrix counts conf[t*C+p] += 1 over the valid region (mIoU);
+ * pixels whose label or prediction is not in [0, C) are ignored. */
 int seg_confusion(const int64_t* pred, const uint8_t* labels, int N, int H, int W, int valid_h,
                   int valid_w, int C, unsigned long long* conf, void* stream);
 

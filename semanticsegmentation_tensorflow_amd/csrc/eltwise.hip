@@ -1077,8 +1077,11 @@ __global__ void confusion_k(const int64_t* __restrict__ pred, const uint8_t* __r
         const int w = (int)(p % W);
         const int h = (int)((p / W) % H);
         if (h >= vh || w >= vw) continue;
-        const int t = lab[p], q = (int)pred[p];
-        if (t < C && q < C) atomicAdd(conf + t * C + q, 1ull);
+        // compared in 64 bits: a negative prediction, or one whose low word
+        // alone is a class, is no class and is ignored like a label >= C
+        const int t = lab[p];
+        const int64_t q = pred[p];
+        if (t < C && q >= 0 && q < C) atomicAdd(conf + t * C + (int)q, 1ull);
     }
 }
 
