@@ -12,6 +12,15 @@ from .ops import round8
 
 
 class PlanMixin:
+    def _users(self, p):
+        """tensor id -> the nodes reading it (as an input or as the fused skip)."""
+        users = {}
+        for n in p.nodes:
+            for t in list(n.inputs) + [n.residual]:
+                if t is not None:
+                    users.setdefault(id(t), []).append(n)
+        return users
+
     def _fold_bn_prologues(self, p, fetched):
         """FC-DenseNet's pre-activation BN -> ReLU -> 1x1 conv
         (Network/model/FCDenseNet.py:25-28, :39-41): a BatchNorm(+ReLU) node
@@ -19,14 +28,9 @@ class PlanMixin:
         prologue -- the BN output is never written (forward) and the filter
         gradient recomputes it from x while staging.  Its backward is
         unchanged (the BN gradient re-derives the mask from x)."""
-        p.folded = set()
         if not self.fold_bn:
             return
-        users = {}
-        for n in p.nodes:
-            for t in list(n.inputs) + [getattr(n, "residual", None)]:
-                if t is not None:
-                    users.setdefault(id(t), []).append(n)
+        users = self._users(p)
         for b in p.nodes:
             if b.kind != "bn" or id(b.output) in fetched:
                 continue
@@ -47,18 +51,11 @@ class PlanMixin:
         re-draw of the mask; when the BN is the conv output's only reader, the
         BN backward applies it (seg_bn_relu_dropout_bwd) and the conv's own
         dropout-gradient pass is skipped.  p.drop_fold: bn node id -> conv."""
-        p.drop_fold = {}
-        p.drop_folded = set()
-        p.bn_before = {}
         if not self.fold_dropout_grad:
             return
-        users = {}
-        for n in p.nodes:
-            for t in list(n.inputs) + [getattr(n, "residual", None)]:
-                if t is not None:
-                    users.setdefault(id(t), []).append(n)
+        users = self._users(p)
         for c in p.nodes:
-            if c.kind != "conv" or c.relu or getattr(c, "kp", None) is None:
+            if c.kind != "conv" or c.relu or c.kp is None:
                 continue
             out = c.output
             if id(out) in fetched:
@@ -76,9 +73,8 @@ class PlanMixin:
         # BN(+ReLU) -> 3x3 conv (FC-DenseNet's growth conv): the conv's input
         # gradient kernel can continue through that BN's backward when the BN
         # output has no other reader and its input gradient is not shared
-        p.bn_before = {}
         for c in p.nodes:
-            if c.kind != "conv" or getattr(c, "pro", None) is not None:
+            if c.kind != "conv" or c.pro is not None:
                 continue
             t = c.inputs[0]
             us = users.get(id(t), [])
@@ -176,18 +172,12 @@ class PlanMixin:
         a part, so that block buffer becomes a channel slice of the decoder
         buffer (offsets compose): the transposed conv writes its slice, the
         block's layers theirs, and neither concat copies."""
-        p.alias = {}          # tensor id -> (root tensor id, channel offset)
-        p.alias_nodes = set()  # ConcatV2 node ids that became views
         if not self.alias_concat:
             return
         nested = {}           # concat output id -> (outer root id, offset): a part of an accepted outer root
         shp = p.shapes
         producer = {id(n.output): n for n in p.nodes}
-        users = {}
-        for n in p.nodes:
-            for t in list(n.inputs) + [getattr(n, "residual", None)]:
-                if t is not None:
-                    users.setdefault(id(t), []).append(n)
+        users = self._users(p)
         fetched = {id(f) for f in p.fetches if isinstance(f, G.Tensor)}
         concats = [n for n in p.nodes if n.kind == "ConcatV2"]
         def part_ok(i):
@@ -224,7 +214,7 @@ class PlanMixin:
                         if u in views or u.kind in ("bn", "ConcatV2"):
                             continue
                         if (g == rid and len(root_users) == 1 and u.kind in ("conv", "tconv")
-                                and u.inputs[0] is root.output and getattr(u, "residual", None) is not root.output):
+                                and u.inputs[0] is root.output and u.residual is not root.output):
                             continue
                         ok = False
             if not ok:
@@ -252,7 +242,6 @@ class PlanMixin:
         ws_need = 0
         p.packs = set()
         p.pack_apad = {}
-        p.pool_idx = {}     # MaxPool node id -> recorded switches (train plans)
         for n in p.nodes:
             y = n.output
             if n.kind == "input":
@@ -320,7 +309,7 @@ class PlanMixin:
                 # (tests/test_session_dryrun.py::test_hwio_only_filter_stays_single_copy).
                 hwio_only = store.hwio_only
                 name = n.w.var_name
-                n.fwd_hwio = (getattr(n, "pro", None) is None and ops.conv2d_fwd_hwio_ok(n.desc)
+                n.fwd_hwio = (n.pro is None and ops.conv2d_fwd_hwio_ok(n.desc)
                               and (name in hwio_only or (self.fwd_hwio and R * S * C * K >= (1 << 23)
                                                          and (name, ops.PACK_KRSC) not in store.packed)))
                 if n.fwd_hwio:
@@ -384,13 +373,10 @@ class PlanMixin:
         (ops.conv2d_fwd_pool) that writes the pooled map and the switches; the
         conv output itself is never materialised (its gradient comes from the
         switches: MaxPoolGrad's fused ReluGrad)."""
-        p.pool_fuse = {}
-        p.pool_fused = set()
         if not self.fuse_pool or self.cdt == ops.F32:
             return
         for n in p.nodes:
-            if (n.kind != "conv" or getattr(n, "pro", None) is not None or n.kp is not None
-                    or getattr(n, "fwd_hwio", False)):
+            if n.kind != "conv" or n.pro is not None or n.kp is not None or n.fwd_hwio:
                 continue
             y = n.output
             cs = consumers.get(id(y), [])
@@ -417,8 +403,6 @@ class PlanMixin:
         The pooled gradient is never written and the MaxPool node's backward
         is skipped.  The pool input has no other consumer, even dims and
         recorded switches.  p.unpool_fuse: conv node id -> MaxPool node."""
-        p.unpool_fuse = {}
-        p.unpool_pools = set()
         if not self.fuse_unpool or self.cdt == ops.F32:
             return
         pos = {id(n): i for i, n in enumerate(p.nodes)}
@@ -432,9 +416,9 @@ class PlanMixin:
             if not cs:
                 continue
             c = min(cs, key=lambda q: pos[id(q)])
-            if c.kind != "conv" or c.inputs[0] is not y or getattr(c, "pro", None) is not None:
+            if c.kind != "conv" or c.inputs[0] is not y or c.pro is not None:
                 continue
-            if getattr(c, "residual", None) is y or sum(1 for q in cs if q is c) != 1:
+            if c.residual is y or sum(1 for q in cs if q is c) != 1:
                 continue
             N, H, W = p.shapes[id(y)][:3]
             if tuple(p.shapes[id(xf)][:3]) != (N, 2 * H, 2 * W):
@@ -451,18 +435,16 @@ class PlanMixin:
         input gradient (conv1_2's, on conv_res64pp) reads those instead of the
         16-bit map: 8 instead of 128 bytes per pixel.  p.mask_bits: producer
         conv id -> uint8 [N, OH, OW, K/8]; p.bits_dgrad: the consumer conv ids."""
-        p.mask_bits = {}
-        p.bits_dgrad = set()
         if not self.relu_bits or self.cdt == ops.F32:
             return
         for n in p.nodes:
             if n.kind != "conv" or id(n) not in p.mask_fuse:
                 continue
-            if (id(n) in p.pool_fuse or id(n) in p.bn_out2 or getattr(n, "pro", None) is not None
-                    or getattr(n, "fwd_hwio", False) or p.buf.get(id(n.output)) is None):
+            if (id(n) in p.pool_fuse or id(n) in p.bn_out2 or n.pro is not None
+                    or n.fwd_hwio or p.buf.get(id(n.output)) is None):
                 continue
             c = consumers[id(n.output)][0]
-            if (c.kind != "conv" or getattr(c, "pro", None) is not None or id(c) in p.bn_before
+            if (c.kind != "conv" or c.pro is not None or id(c) in p.bn_before
                     or id(c) in p.unpool_fuse or id(n.output) in p.alias):
                 continue
             if not (ops.conv2d_fwd_relu_bits_ok(n.desc) and ops.conv2d_bwd_data_bits_ok(c.desc)):
@@ -480,8 +462,6 @@ class PlanMixin:
         forward pass -- a full re-read of the conv output -- is skipped.  The
         conv output is still written: the BN backward re-derives its ReLU mask
         and dgamma from it.  p.bn_out2: conv node id -> BN node."""
-        p.bn_out2 = {}
-        p.bn_out2_done = set()
         if not self.fuse_bn_out or self.cdt == ops.F32:
             return
         producer = {id(n.output): n for n in p.nodes if n.kind == "conv"}
@@ -489,32 +469,23 @@ class PlanMixin:
             if b.kind != "bn" or id(b) in p.folded or id(b.output) in p.fetched:
                 continue
             c = producer.get(id(b.inputs[0]))
-            if (c is None or id(c) in p.pool_fuse or id(c) in p.bn_out2 or id(c.output) in p.fetched
-                    or getattr(c, "fwd_hwio", False)):
+            if c is None or id(c) in p.pool_fuse or id(c) in p.bn_out2 or id(c.output) in p.fetched or c.fwd_hwio:
                 continue
             cs = consumers.get(id(c.output), [])
             if len(cs) != 1 or cs[0] is not b.ops[0]:
                 continue
             if p.buf.get(id(c.output)) is None or p.buf.get(id(b.output)) is None:
                 continue
-            if not ops.conv2d_fwd_bn2_ok(c.desc, getattr(c, "pro", None) is not None):
+            if not ops.conv2d_fwd_bn2_ok(c.desc, c.pro is not None):
                 continue
             p.bn_out2[id(c)] = b
             p.bn_out2_done.add(id(b))
 
     def _plan_backward(self, p):
-        dev = self.device
-        grad = {}
-        p.grad = grad
-        p.tmp = {}
         # grads of variables go to the flat buffer; activations get their own
         covered = set()
         for n in p.nodes:
-            if n.kind == "conv":
-                covered.add(n.w.var_name)
-                if n.bias is not None:
-                    covered.add(n.bias.var_name)
-            elif n.kind == "tconv":
+            if n.kind in ("conv", "tconv"):
                 covered.add(n.w.var_name)
                 if n.bias is not None:
                     covered.add(n.bias.var_name)
@@ -529,11 +500,11 @@ class PlanMixin:
         p.producer = {id(n.output): n for n in p.nodes}
         consumers = {}
         for n in p.nodes:
-            ins = list(n.inputs) + ([n.residual] if getattr(n, "residual", None) is not None else []) \
-                + ([n.labels] if getattr(n, "labels", None) is not None else [])
+            ins = list(n.inputs) + ([n.residual] if n.residual is not None else []) \
+                + ([n.labels] if n.labels is not None else [])
             for t in ins:
                 consumers.setdefault(id(t), []).append(n)
-        p.mask_fuse = set()
+        p.ncons = {t: len(cs) for t, cs in consumers.items()}
         for n in p.nodes:
             if n.kind != "conv" or not n.relu or id(n.output) not in p.needs_grad:
                 continue
@@ -545,8 +516,6 @@ class PlanMixin:
                 p.mask_fuse.add(id(n))
         self._plan_unpool_fusion(p, consumers)
         self._plan_relu_bits(p, consumers)
-        p.adam_fusable = set()
-        p.wg_ws = {}                     # per-conv filter-gradient workspace (pending split-K slabs)
         for n in p.nodes:
             if n.kind == "conv" and ops.wgrad_adam_fusable(n.desc):
                 p.adam_fusable.add(id(n))

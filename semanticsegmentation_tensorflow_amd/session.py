@@ -17,17 +17,20 @@ Compilation (per fetch set and fed shapes):
     rest of backward;
   * TF1 Adam over the flat buffer, then re-packing of the bf16/fp32 filter
     copies the convolution kernels read.
+
+Here: run, the train-step surfaces, compilation into nodes and the step's top
+level (`_execute`).  `Session` inherits the rest as mixins: planner.py (plans),
+forward.py / backward.py (the launches, per node kind), streams.py (side stream).
 """
 from __future__ import annotations
-
-import collections
 
 import numpy as np
 import torch
 
 from . import graph as G
 from . import ops
-from .ops import round8
+from .backward import BackwardMixin
+from .forward import ForwardMixin
 from .planner import PlanMixin
 from .streams import StreamMixin, _AdamOverlap
 from .variables import VariableStore
@@ -43,11 +46,51 @@ class _Node:
         self.ops = ops_
         self.inputs = inputs
         self.output = output
+        # filled by _compile (kw) or the planner for some kinds only
+        self.pro = None          # conv: the BatchNorm(+ReLU) node folded into its operand prologue
+        self.fwd_hwio = False    # conv: the forward reads the HWIO packed copy
+        self.residual = None     # tconv: the skip tensor added in its epilogue
+        self.labels = None       # xent
+        self.kp = None           # conv: keep_prob of the dropout in its epilogue (tensor or number)
+        self.kp_val = None       # conv / Dropout: this step's keep_prob and seed (set by the forward)
+        self.seed_val = None
         self.__dict__.update(kw)
 
 
 class Plan:
-    pass
+    """The static launch plan of one fetch set at one set of fed shapes: the sets
+    and dicts the executor reads start empty, planner.py fills those that apply."""
+
+    def __init__(self):
+        self.folded = set()        # BN node ids applied by their consumer conv's operand prologue
+        self.drop_fold = {}        # BN node id -> conv whose dropout gradient the BN backward applies
+        self.drop_folded = set()   # those convs' ids
+        self.bn_before = {}        # growth conv id -> the BN node producing its input
+        self.alias = {}            # tensor id -> (root tensor id, channel offset)
+        self.alias_nodes = set()   # ConcatV2 node ids that became views
+        self.pool_idx = {}         # MaxPool node id -> recorded switches (train plans)
+        self.pool_fuse = {}        # conv id -> MaxPool node run in its pooled epilogue
+        self.pool_fused = set()    # those MaxPool nodes' ids
+        self.bn_out2 = {}          # conv id -> BN node whose output the conv launch also writes
+        self.bn_out2_done = set()  # those BN nodes' ids
+        self.unpool_fuse = {}      # conv id -> MaxPool node whose gradient runs in its dgrad epilogue
+        self.unpool_pools = set()  # those MaxPool nodes' ids
+        self.mask_fuse = set()     # ReLU conv ids whose gradient arrives already masked
+        self.mask_bits = {}        # producer conv id -> its ReLU mask as bits
+        self.bits_dgrad = set()    # consumer conv ids whose input gradient reads those bits
+        self.adam_fusable = set()  # conv ids that can take the fused filter-gradient + Adam launch
+        self.wg_ws = {}            # conv / tconv id -> its filter-gradient workspace (pending split-K slabs)
+        self.producer = {}         # tensor id -> node
+        self.ncons = {}            # tensor id -> number of consuming nodes
+        self.tmp = {}              # persistent scratch buffers of the backward, by key
+        self.bn_batch = None       # ops.BnFinishBatch of the deferred BN-backward finishes
+
+    def scratch(self, key, make, *args, **kw):
+        """The persistent buffer `key`, allocated as make(*args, **kw) on first use."""
+        t = self.tmp.get(key)
+        if t is None:
+            t = self.tmp[key] = make(*args, **kw)
+        return t
 
 
 def _is_op(f, type_):
@@ -84,12 +127,6 @@ class _TrainSpec:
         self.ops = ops_
 
 
-def _np(x):
-    if isinstance(x, torch.Tensor):
-        return x
-    return torch.from_numpy(np.ascontiguousarray(x))
-
-
 _SIDE_STREAMS = {}
 
 
@@ -114,7 +151,7 @@ def side_stream_for(device):
     return s
 
 
-class Session(PlanMixin, StreamMixin):
+class Session(PlanMixin, ForwardMixin, BackwardMixin, StreamMixin):
     def __init__(self, graph=None, compute_dtype="bf16", device=None, seed=0, data_parallel=None,
                  overlap_optimizer=False, fuse_adam=True, loss_scale=None):
         """compute_dtype: "bf16" (default), "f16" (IEEE half activations and
@@ -375,7 +412,6 @@ class Session(PlanMixin, StreamMixin):
     # --------------------------------------------------------------- compile
     def _compile(self, fetches, feed_dict):
         g = self.graph
-        store = self.store
         p = Plan()
         p.fetches = fetches
         p.train = self._train_spec(fetches)
@@ -429,12 +465,31 @@ class Session(PlanMixin, StreamMixin):
                     needs_grad.add(id(op.outputs[0]))
         p.needs_grad = needs_grad
 
-        # ---- fusion into nodes
+        p.nodes = self._fuse_nodes(order, consumers, fetched, shp)
+        p.fetched = fetched
+        self._fold_bn_prologues(p, fetched)
+        self._fold_dropout_grads(p, fetched)
+        self._allocate(p, consumers, feeds)
+        return p
+
+    def _fuse_nodes(self, order, consumers, fetched, shp):
+        """Fusion of single-consumer op chains into nodes (one launch each)."""
         def single_consumer(t, type_):
             cs = consumers.get(id(t), [])
             if len(cs) == 1 and cs[0].type == type_ and id(t) not in fetched:
                 return cs[0]
             return None
+
+        def absorb(chain, type_):
+            """Append the chain output's only consumer when it is a `type_` op
+            reading it as its first input; that op, or None."""
+            cur = chain[-1].outputs[0]
+            nxt = single_consumer(cur, type_)
+            if nxt is None or nxt.inputs[0] is not cur:
+                return None
+            chain.append(nxt)
+            absorbed.add(nxt.id)
+            return nxt
 
         absorbed = set()
         nodes = []
@@ -446,67 +501,39 @@ class Session(PlanMixin, StreamMixin):
             if t == "Conv2D":
                 x, w = op.inputs
                 chain = [op]
-                bias = relu = None
-                kp = None
-                cur = y
-                nxt = single_consumer(cur, "BiasAdd")
-                if nxt is not None and nxt.inputs[0] is cur:
-                    bias = nxt.inputs[1]
-                    chain.append(nxt)
-                    cur = nxt.outputs[0]
-                nxt = single_consumer(cur, "Relu")
-                if nxt is not None:
-                    relu = True
-                    chain.append(nxt)
-                    cur = nxt.outputs[0]
-                if relu or self.fuse_dropout:
-                    # Conv [+BiasAdd] [+Relu] + Dropout: applied in the epilogue (without
-                    # a ReLU the gradient re-draws the mask: seg_dropout_bwd_ch)
-                    nxt = single_consumer(cur, "Dropout")
-                    if nxt is not None:
-                        kp = nxt.attrs["keep_prob"]
-                        chain.append(nxt)
-                        cur = nxt.outputs[0]
-                for c in chain[1:]:
-                    absorbed.add(c.id)
-                nodes.append(_Node("conv", chain, [x], cur, w=w, bias=bias, relu=bool(relu), kp=kp,
+                b = absorb(chain, "BiasAdd")
+                relu = absorb(chain, "Relu") is not None
+                # Conv [+BiasAdd] [+Relu] + Dropout: applied in the epilogue (without
+                # a ReLU the gradient re-draws the mask: seg_dropout_bwd_ch)
+                d = absorb(chain, "Dropout") if (relu or self.fuse_dropout) else None
+                nodes.append(_Node("conv", chain, [x], chain[-1].outputs[0], w=w,
+                                   bias=b.inputs[1] if b is not None else None, relu=relu,
+                                   kp=d.attrs["keep_prob"] if d is not None else None,
                                    stride=op.attrs["stride"], dilation=op.attrs["dilation"],
                                    dilation_hw=op.attrs["dilation_hw"], padding=op.attrs["padding"]))
             elif t == "Conv2DTranspose":
                 x, w = op.inputs
                 chain = [op]
-                bias = res = None
-                cur = y
-                nxt = single_consumer(cur, "BiasAdd")
-                if nxt is not None and nxt.inputs[0] is cur:
-                    bias = nxt.inputs[1]
-                    chain.append(nxt)
-                    cur = nxt.outputs[0]
+                b = absorb(chain, "BiasAdd")
+                res = None
+                cur = chain[-1].outputs[0]
                 nxt = single_consumer(cur, "Add")
                 if nxt is not None:
-                    a, b = nxt.inputs
-                    other = b if a is cur else a
+                    a0, a1 = nxt.inputs
+                    other = a1 if a0 is cur else a0
                     if shp[id(other)] == shp[id(nxt.outputs[0])] and other is not cur:
                         res = other
                         chain.append(nxt)
-                        cur = nxt.outputs[0]
-                for c in chain[1:]:
-                    absorbed.add(c.id)
-                nodes.append(_Node("tconv", chain, [x], cur, w=w, bias=bias, residual=res,
+                        absorbed.add(nxt.id)
+                nodes.append(_Node("tconv", chain, [x], chain[-1].outputs[0], w=w,
+                                   bias=b.inputs[1] if b is not None else None, residual=res,
                                    stride=op.attrs["stride"], padding=op.attrs["padding"],
                                    output_shape=op.attrs["output_shape"]))
             elif t == "FusedBatchNorm":
                 x, gamma, beta = op.inputs
                 chain = [op]
-                cur = y
-                relu = False
-                nxt = single_consumer(cur, "Relu")
-                if nxt is not None:
-                    relu = True
-                    chain.append(nxt)
-                    cur = nxt.outputs[0]
-                    absorbed.add(nxt.id)
-                nodes.append(_Node("bn", chain, [x], cur, gamma=gamma, beta=beta, relu=relu,
+                relu = absorb(chain, "Relu") is not None
+                nodes.append(_Node("bn", chain, [x], chain[-1].outputs[0], gamma=gamma, beta=beta, relu=relu,
                                    eps=op.attrs["epsilon"]))
             elif t == "SoftmaxXent":
                 logits, labels = op.inputs
@@ -525,12 +552,7 @@ class Session(PlanMixin, StreamMixin):
                 raise NotImplementedError("reduce_mean is only supported on the xent loss")
             else:
                 raise NotImplementedError(f"op {t} is not on the hot path")
-        p.nodes = nodes
-        p.fetched = fetched
-        self._fold_bn_prologues(p, fetched)
-        self._fold_dropout_grads(p, fetched)
-        self._allocate(p, consumers, feeds)
-        return p
+        return nodes
 
     @property
     def _dpa(self):
@@ -634,37 +656,9 @@ class Session(PlanMixin, StreamMixin):
             segs.append((store.offset[v.var_name], rs, a, b, rows, tr))
         return segs
 
-    def _feed(self, p, feed_dict):
-        feeds = {id(k): v for k, v in feed_dict.items()}
-        # scalars (keep_probability) are read at launch time, not staged
-        scal = {id(k): float(v) for k, v in feed_dict.items() if np.ndim(v) == 0}
-        for tid, (kind, stage) in p.feed_slots.items():
-            v = feeds[tid]
-            if kind == "scalar":
-                scal[tid] = float(v)
-                continue
-            src = _np(v)
-            if kind == "image" and src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous() \
-                    and src.shape == stage.shape:
-                ops.prepare_input(src, p.buf[tid])   # augmented uint8 batch resident in HBM
-                continue
-            if src.is_cuda and src.dtype == stage.dtype and src.is_contiguous() and src.shape == stage.shape:
-                src_dev = src                      # resident in HBM: no copy
-            else:
-                stage.copy_(src.to(stage.dtype) if src.dtype != stage.dtype else src, non_blocking=True)
-                src_dev = stage
-            if kind == "image":
-                ops.prepare_input(src_dev, p.buf[tid])
-            else:
-                p.buf[tid] = src_dev
-        return scal
-
-    def _kp(self, kp, scal):
-        if kp is None:
-            return 1.0
-        if isinstance(kp, G.Tensor):
-            return scal[id(kp)]
-        return float(kp)
+    def _pack(self, n, mode):
+        """The packed compute copy (layout `mode`) of conv / tconv node n's filter."""
+        return self.store.packed[(n.w.var_name, mode)][0]
 
     def _execute(self, p, feed_dict):
         self.run_count += 1
@@ -674,229 +668,132 @@ class Session(PlanMixin, StreamMixin):
         self._repack(p)
         self._check_bn_stats(p)
         scal = self._feed(p, feed_dict)
-        buf = p.buf
-        store = self.store
         step_seed = (self.seed * 1000003 + self.run_count * 7919) & 0xFFFFFFFF
         if self.dp is not None:
             step_seed ^= (self.dp.rank + 1) * _SEED_MIX
-        out = {}
-        # ---------------- forward
-        for i, n in enumerate(p.nodes):
-            k = n.kind
-            if k == "input":
-                continue
-            y = buf[id(n.output)]
-            if k == "conv":
-                x = buf[id(n.inputs[0])]
-                kp = self._kp(n.kp, scal)
-                n.kp_val = kp
-                n.seed_val = (step_seed + i * 131) & 0xFFFFFFFF
-                epi = ops.epilogue(bias=store.param(n.bias.var_name) if n.bias is not None else None,
-                                   relu=n.relu, keep_prob=kp, seed=n.seed_val)
-                if id(n) in p.bn_out2:
-                    b2 = p.bn_out2[id(n)]
-                    b = getattr(n, "pro", None)
-                    self._timed(n.desc, ops.OP_FWD_PRO if b is not None else ops.OP_FWD, ops.conv2d_fwd_bn2, n.desc,
-                                x if b is None else buf[id(b.inputs[0])], None if b is None else self._prologue(b),
-                                store.packed[(n.w.var_name, ops.PACK_KRSC)][0], y, buf[id(b2.output)],
-                                store.param(b2.gamma.var_name), store.param(b2.beta.var_name), b2.relu, b2.eps,
-                                epi, self.ws)
-                elif getattr(n, "pro", None) is not None:
-                    b = n.pro
-                    self._timed(n.desc, ops.OP_FWD_PRO, ops.conv2d_fwd_pro, n.desc, buf[id(b.inputs[0])],
-                                self._prologue(b), store.packed[(n.w.var_name, ops.PACK_KRSC)][0], y, epi, self.ws)
-                elif id(n) in p.pool_fuse:
-                    m = p.pool_fuse[id(n)]
-                    self._timed(n.desc, ops.OP_FWD, ops.conv2d_fwd_pool, n.desc, x,
-                                store.packed[(n.w.var_name, ops.PACK_KRSC)][0], buf[id(m.output)],
-                                p.pool_idx.get(id(m)), epi, self.ws)
-                elif getattr(n, "fwd_hwio", False):
-                    self._timed(n.desc, ops.OP_FWD, ops.conv2d_fwd_hwio, n.desc, x,
-                                store.packed[(n.w.var_name, ops.PACK_HWIO)][0], y, epi, self.ws)
-                elif id(n) in getattr(p, "mask_bits", {}):
-                    self._timed(n.desc, ops.OP_FWD, ops.conv2d_fwd_relu_bits, n.desc, x,
-                                store.packed[(n.w.var_name, ops.PACK_KRSC)][0], y, p.mask_bits[id(n)], epi)
-                else:
-                    self._timed(n.desc, ops.OP_FWD, ops.conv2d_fwd, n.desc, x,
-                                store.packed[(n.w.var_name, ops.PACK_KRSC)][0], y, epi, self.ws)
-            elif k == "tconv":
-                x = buf[id(n.inputs[0])]
-                res = buf[id(n.residual)] if n.residual is not None else None
-                epi = ops.epilogue(bias=store.param(n.bias.var_name) if n.bias is not None else None,
-                                   residual=res)
-                self._timed(n.desc, ops.OP_TFWD, ops.tconv2d_fwd, n.desc, x,
-                            store.packed[(n.w.var_name, ops.PACK_TCONV_FWD)][0], y, epi, self.ws)
-            elif k == "MaxPool":
-                idx = p.pool_idx.get(id(n))
-                if id(n) in p.pool_fused:
-                    pass                       # written by the producing conv's pooled epilogue
-                elif idx is not None:
-                    ops.maxpool2x2_fwd_argmax(buf[id(n.inputs[0])], y, idx)
-                else:
-                    ops.maxpool2x2_fwd(buf[id(n.inputs[0])], y)
-            elif k == "AvgPool":
-                ops.avgpool2x2_fwd(buf[id(n.inputs[0])], y)
-            elif k == "Add":
-                ops.add(buf[id(n.inputs[0])], buf[id(n.inputs[1])], y)
-            elif k == "bn":
-                if id(n) in p.folded or id(n) in p.bn_out2_done:
-                    continue                        # applied by its conv's operand prologue / written by its conv
-                C = p.shapes[id(n.inputs[0])][3]
-                ops.bn_relu_fwd(buf[id(n.inputs[0])], y, store.param(n.gamma.var_name),
-                                store.param(n.beta.var_name), C, n.relu, n.eps)
-            elif k == "Relu":
-                self._relu_fwd(buf[id(n.inputs[0])], y)
-            elif k == "Dropout":
-                kp = self._kp(n.ops[0].attrs["keep_prob"], scal)
-                n.kp_val = kp
-                n.seed_val = (step_seed + i * 131) & 0xFFFFFFFF
-                if kp < 1.0:
-                    ops.dropout_fwd(buf[id(n.inputs[0])], y, kp, n.seed_val)
-                else:
-                    ops.copy_channels(buf[id(n.inputs[0])], y)
-            elif k == "xent":
-                lg = buf[id(n.inputs[0])]
-                labels = buf[id(n.labels)]
-                ops.softmax_xent(lg, labels, n.dlogits, n.loss_sum, n.num_classes, n.valid_hw,
-                                 grad_scale=(self.loss_scale if p.train else 1.0) / n.count, ws=self.ws)
-            elif k == "ConcatV2":
-                if id(n) not in p.alias_nodes:      # aliased: the parts already sit in place
-                    ops.concat_fwd([(buf[id(t)], p.shapes[id(t)][3]) for t in n.inputs], y,
-                                   p.shapes[id(n.output)][3])
-            elif k == "ArgMax":
-                x = buf[id(n.inputs[0])]
-                C = p.shapes[id(n.inputs[0])][3]
-                ops.argmax(x, y.view(-1), C)
-            elif k == "Softmax":
-                ops.softmax(buf[id(n.inputs[0])], y, p.shapes[id(n.inputs[0])][3])
-            elif k == "ResizeBilinear":
-                x = buf[id(n.inputs[0])]
-                if x.shape[1] == 1 and x.shape[2] == 1:      # align_corners from 1x1: a broadcast
-                    ops.spatial_broadcast(x, y, 1.0)
-                else:
-                    ops.resize_bilinear_fwd(x, y)
-            elif k == "GlobalAvgPool":
-                x = buf[id(n.inputs[0])]
-                ops.spatial_reduce(x, y, 1.0 / (x.shape[1] * x.shape[2]), self.ws)
-            elif k == "ExpandDims":
-                pass
-            else:
-                raise NotImplementedError(k)
-        # ---------------- backward + optimizer
+        self._forward(p, scal, step_seed)
         if p.train:
-            ts = p.train.attrs
-            opt = ts["optimizer"]
-            dpa = self._dpa
-            world = dpa.world if dpa is not None else 1
-            S = self.loss_scale                     # the scale this step's loss gradient carries
-            scaled = S != 1.0
-            gs = ts["grad_scale"] / world / S
-            if scaled and self.overlap_optimizer:
-                raise NotImplementedError("loss scaling needs the whole gradient checked before any update")
-            if opt is not None:
-                store.step += 1
-            self._fused = None
-            if opt is not None and self.fuse_adam and dpa is None and not self.overlap_optimizer \
-                    and not scaled and p.adam_fusable:
-                self._fused = (opt, gs, set())
-            # ZeRO-1 exchange for an Adam step (dp.py); the accumulate template
-            # and the overlapped per-layer optimizer read whole gradients
-            zero = (dpa is not None and dpa.shard and opt is not None and not self.overlap_optimizer
-                    and not p.train.accum)
+            self._train_step(p, scal)
+        return self._fetch(p)
+
+    def _train_step(self, p, scal):
+        """Backward and optimizer: set-up, backward, loss-scale outcome, update."""
+        store = self.store
+        ts = p.train.attrs
+        opt = ts["optimizer"]
+        dpa = self._dpa
+        world = dpa.world if dpa is not None else 1
+        S = self.loss_scale                     # the scale this step's loss gradient carries
+        scaled = S != 1.0
+        gs = ts["grad_scale"] / world / S
+        if scaled and self.overlap_optimizer:
+            raise NotImplementedError("loss scaling needs the whole gradient checked before any update")
+        if opt is not None:
+            store.step += 1
+        self._fused = None
+        if opt is not None and self.fuse_adam and dpa is None and not self.overlap_optimizer \
+                and not scaled and p.adam_fusable:
+            self._fused = (opt, gs, set())
+        # ZeRO-1 exchange for an Adam step (dp.py); the accumulate template
+        # and the overlapped per-layer optimizer read whole gradients
+        zero = (dpa is not None and dpa.shard and opt is not None and not self.overlap_optimizer
+                and not p.train.accum)
+        if dpa is not None:
+            dpa.mode = "zero" if zero else "allreduce"
+            if opt is not None and not zero and dpa.slots_stale:
+                # a whole-variable Adam after ZeRO-1 steps: gather the m / v
+                # slices of the other ranks first, or the replicas diverge
+                self.sync_optimizer_slots()
+        self._red = None
+        if self.defer_wgrad_reduce and self.device.type == "cuda":
+            # (with the overlapped optimizer the reductions and each layer's
+            # Adam share the side stream: a layer's reduction precedes its update)
+            self._red = (self.side_stream(), torch.cuda.current_stream(self.device))
             if dpa is not None:
-                dpa.mode = "zero" if zero else "allreduce"
-                if opt is not None and not zero and dpa.slots_stale:
-                    # a whole-variable Adam after ZeRO-1 steps: gather the m / v
-                    # slices of the other ranks first, or the replicas diverge
-                    self.sync_optimizer_slots()
-            self._red = None
-            if self.defer_wgrad_reduce and self.device.type == "cuda":
-                # (with the overlapped optimizer the reductions and each layer's
-                # Adam share the side stream: a layer's reduction precedes its update)
-                self._red = (self.side_stream(), torch.cuda.current_stream(self.device))
-                if dpa is not None:
-                    dpa.launch_streams = self._red
-            if opt is not None and self.overlap_optimizer and self.device.type == "cuda":
-                # per-layer Adam on a side stream as soon as the layer's gradient is final
-                self._adam_ctx = _AdamOverlap(self, opt, gs, p.var_set)
-                if dpa is not None:
-                    dpa.on_launch = self._adam_ctx.after_work
-            elif (opt is not None and dpa is not None and not zero and self.overlap_big_mb and not scaled
-                  and not p.train.accum and self.device.type == "cuda"):
-                self._adam_ctx = _AdamOverlap(self, opt, gs, p.var_set, big_only=True)
+                dpa.launch_streams = self._red
+        if opt is not None and self.overlap_optimizer and self.device.type == "cuda":
+            # per-layer Adam on a side stream as soon as the layer's gradient is final
+            self._adam_ctx = _AdamOverlap(self, opt, gs, p.var_set)
+            if dpa is not None:
                 dpa.on_launch = self._adam_ctx.after_work
-            if dpa is not None and p.never_ready:
-                dpa.ready(p.never_ready)
-            self._ready_filter = p.var_set
-            ok = False
-            try:
-                self._backward(p, scal)
-                self._tick_fused(flush=True)
-                ok = True
-            finally:
-                # on an exception: no stale fused conv6 / conv7 update is left
-                # for the next step, and the compute stream does not run ahead
-                # of side-stream kernels still reading this step's buffers
-                self._ready_filter = None
-                if not ok:
-                    self._pending_fused = []
-                    self._fused = None
-                    self._adam_ctx = None
-                if self._red is not None:        # pending filter-gradient reductions done before Adam
-                    self._red[1].wait_stream(self._red[0])
-                    self._red = None
-                if dpa is not None:
-                    if ok:
-                        dpa.finish()
-                    else:
-                        dpa.abort_step()
-                    dpa.on_launch = None
-                    dpa.launch_streams = None
-            if scaled and not self._grads_finite():
-                # overflow in the scaled fp16 gradients: no update this step
-                # (TF LossScaleOptimizer), halve the scale
-                self.skipped_steps += 1
-                if opt is not None:
-                    store.step -= 1
-                self.loss_scale = max(self.loss_scale / 2.0, 1.0)
-                self.good_steps = 0
-                opt = None
-                p_accum = []
-            else:
-                p_accum = p.train.accum
-                if scaled and self.dynamic_scale:
-                    self.good_steps += 1
-                    if self.good_steps >= self.scale_increment_period:
-                        self.loss_scale *= 2.0
-                        self.good_steps = 0
-            if opt is None:
-                # accumulate template: accum += const * grad (Network/main.py:92-95)
-                for acc, var, sc in p_accum:
-                    ops.axpy(store.aux[acc].view(-1), store.grad(var).view(-1), sc / world / S)
-                store.aux_version += 1
-            elif self._adam_ctx is not None:
-                self._adam_ctx.finish()
+        elif (opt is not None and dpa is not None and not zero and self.overlap_big_mb and not scaled
+              and not p.train.accum and self.device.type == "cuda"):
+            self._adam_ctx = _AdamOverlap(self, opt, gs, p.var_set, big_only=True)
+            dpa.on_launch = self._adam_ctx.after_work
+        if dpa is not None and p.never_ready:
+            dpa.ready(p.never_ready)
+        self._ready_filter = p.var_set
+        ok = False
+        try:
+            self._backward(p, scal)
+            self._tick_fused(flush=True)
+            ok = True
+        finally:
+            # on an exception: no stale fused conv6 / conv7 update is left
+            # for the next step, and the compute stream does not run ahead
+            # of side-stream kernels still reading this step's buffers
+            self._ready_filter = None
+            if not ok:
+                self._pending_fused = []
+                self._fused = None
                 self._adam_ctx = None
-            elif zero:
-                self._zero_update(p, opt, gs)
-            else:
-                done = self._fused[2] if self._fused is not None else set()
-                rest = [nm for nm in p.adam_names if nm not in done]
-                if rest:
-                    ops.adam_tf1_pack(store.params, store.grads, store.m, store.v, self._adam_plan(rest), opt.lr,
-                                      store.step, opt.beta1, opt.beta2, opt.epsilon, grad_scale=gs,
-                                      dtype=self._pack_dtype())
-            self._fused = None
+            if self._red is not None:        # pending filter-gradient reductions done before Adam
+                self._red[1].wait_stream(self._red[0])
+                self._red = None
+            if dpa is not None:
+                if ok:
+                    dpa.finish()
+                else:
+                    dpa.abort_step()
+                dpa.on_launch = None
+                dpa.launch_streams = None
+        if scaled and not self._grads_finite():
+            # overflow in the scaled fp16 gradients: no update this step
+            # (TF LossScaleOptimizer), halve the scale
+            self.skipped_steps += 1
             if opt is not None:
-                store.version += 1
-                self._packed_version = store.version
-                self._bump_global_step(ts.get("global_step"))
-        # ---------------- fetch values
+                store.step -= 1
+            self.loss_scale = max(self.loss_scale / 2.0, 1.0)
+            self.good_steps = 0
+            opt = None
+            p_accum = []
+        else:
+            p_accum = p.train.accum
+            if scaled and self.dynamic_scale:
+                self.good_steps += 1
+                if self.good_steps >= self.scale_increment_period:
+                    self.loss_scale *= 2.0
+                    self.good_steps = 0
+        if opt is None:
+            # accumulate template: accum += const * grad (Network/main.py:92-95)
+            for acc, var, sc in p_accum:
+                ops.axpy(store.aux[acc].view(-1), store.grad(var).view(-1), sc / world / S)
+            store.aux_version += 1
+        elif self._adam_ctx is not None:
+            self._adam_ctx.finish()
+            self._adam_ctx = None
+        elif zero:
+            self._zero_update(p, opt, gs)
+        else:
+            done = self._fused[2] if self._fused is not None else set()
+            rest = [nm for nm in p.adam_names if nm not in done]
+            if rest:
+                ops.adam_tf1_pack(store.params, store.grads, store.m, store.v, self._adam_plan(rest), opt.lr,
+                                  store.step, opt.beta1, opt.beta2, opt.epsilon, grad_scale=gs,
+                                  dtype=self._pack_dtype())
+        self._fused = None
+        if opt is not None:
+            store.version += 1
+            self._packed_version = store.version
+            self._bump_global_step(ts.get("global_step"))
+
+    def _fetch(self, p):
+        out = {}
         for f in p.fetches:
             if isinstance(f, G.Op):
                 out[id(f)] = None
                 continue
-            t = buf.get(id(f))
+            t = p.buf.get(id(f))
             node = next((n for n in p.nodes if n.output is f), None)
             if node is not None and node.kind == "xent":
                 out[id(f)] = (t / node.count).reshape(())
@@ -907,574 +804,8 @@ class Session(PlanMixin, StreamMixin):
                 out[id(f)] = t[..., :C].float()
         return out
 
-    def _relu_fwd(self, x, y):
-        C = x.shape[-1]
-        one = torch.ones(C, dtype=torch.float32, device=self.device)
-        zero = torch.zeros(C, dtype=torch.float32, device=self.device)
-        ops.bn_relu_fwd(x, y, one, zero, C, True, eps=0.0)
-
     def _pack_dtype(self):
         return self.cdt
-
-    def _grad_ready(self, names):
-        """The gradients of `names` are final once the kernels enqueued so far
-        run: hand them to the all-reduce (DP) or straight to the overlapped
-        optimizer."""
-        if self._ready_filter is not None:
-            names = [nm for nm in names if nm in self._ready_filter]
-        if self._dpa is not None:
-            self.dp.ready(names)
-        elif self._adam_ctx is not None:
-            self._adam_ctx.launch(names)
-
-    def _mask_epi(self, p, x):
-        """Epilogue fusing the ReluGrad (x 1/keep_prob) of x's producer into the
-        input-gradient kernel of x's (only) consumer, or None."""
-        prod = p.producer.get(id(x))
-        if prod is None or id(prod) not in p.mask_fuse:
-            return None
-        kp = prod.kp_val
-        scale = 1.0 / kp if (kp is not None and kp < 1.0) else 1.0
-        return ops.epilogue(relu_mask=p.buf[id(x)], mask_scale=scale)
-
-    # ------------------------------------------------------------- backward
-    def _backward(self, p, scal):
-        buf = p.buf
-        store = self.store
-        grad = {}
-        ws = self.ws
-        ng = p.needs_grad
-
-        def zeros_for(t):
-            # (a pool-fused conv's output has no buffer: only its shape)
-            return torch.zeros_like(buf[id(t)]) if buf[id(t)] is not None else self._act(p.shapes[id(t)])
-
-        def dest(t):
-            """(buffer to write t's gradient into, accumulate-after flag)."""
-            if id(t) not in grad:
-                gbuf = p.tmp.get(("g", id(t)))
-                if gbuf is None:
-                    gbuf = zeros_for(t)
-                    p.tmp[("g", id(t))] = gbuf
-                grad[id(t)] = gbuf
-                return gbuf, None
-            tmp = p.tmp.get(("acc", id(t)))
-            if tmp is None:
-                tmp = zeros_for(t)
-                p.tmp[("acc", id(t))] = tmp
-            return tmp, grad[id(t)]
-
-        def done(dst, acc):
-            if acc is not None:
-                ops.add(acc, dst, acc)
-
-        def gdst(name):
-            """Where a variable's gradient is written: its slice of the flat
-            buffer when it is in var_list; otherwise a scratch sink, so the
-            slices the data-parallel buckets release up front (never_ready) are
-            not written while their all-reduce may be reading them."""
-            if name in p.var_set:
-                return store.grad(name)
-            t = p.tmp.get(("gscratch", name))
-            if t is None:
-                t = torch.zeros_like(store.grad(name))
-                p.tmp[("gscratch", name)] = t
-            return t
-
-        ginit = set()      # aliased-concat roots whose gradient buffer holds data this step
-
-        # deferred BN-backward finishes: (segment, variable names) per fused launch
-        bn_defer = ([] if (self.defer_bn_finish and self._dpa is None and self._adam_ctx is None
-                           and self.device.type == "cuda") else None)
-
-        def bn_part(n):
-            """Persistent partial-row buffer of node n's fused BN backward."""
-            t = p.tmp.get(("bnpart", id(n)))
-            if t is None:
-                t = torch.empty(max(1, ops.conv_bwd_data_bn_part_rows(n.desc)) * 2 * n.desc.C,
-                                dtype=torch.float32, device=self.device)
-                p.tmp[("bnpart", id(n))] = t
-            return t
-
-        def adest(t):
-            """Slice of the root's gradient buffer for aliased t, and whether the
-            kernel must accumulate into it (False only for the first write
-            when it covers the whole root)."""
-            r, off = p.alias[id(t)]
-            dB = p.tmp.get(("ga", r))
-            if dB is None:
-                dB = torch.zeros_like(buf[r])
-                p.tmp[("ga", r)] = dB
-            C = p.shapes[id(t)][3]
-            view = dB[..., off:off + C]
-            grad[id(t)] = view
-            if r not in ginit:
-                ginit.add(r)
-                if off == 0 and C == p.shapes[r][3]:
-                    return view, False
-                dB.zero_()
-            return view, True
-
-        if not hasattr(p, "ncons"):
-            p.ncons = collections.Counter(id(i) for m in p.nodes
-                                          for i in list(m.inputs) + [getattr(m, "residual", None)] if i is not None)
-
-        def contribute_alias(t, g):
-            if id(t) not in ng:
-                return
-            if id(t) not in grad:
-                # share the buffer only when no later contribution will add into
-                # it (side-stream filter gradients may still be reading g)
-                grad[id(t)] = g if p.ncons[id(t)] <= 1 else g.clone()
-            else:
-                ops.add(grad[id(t)], g, grad[id(t)])
-
-        main_wg = set()
-        if self._red is not None and self.main_wgrad > 0:
-            convs = [m for m in p.nodes if m.kind == "conv" and m.w.var_name in p.var_set
-                     and getattr(m, "pro", None) is None and id(m) not in p.adam_fusable]
-            main_wg = {id(m) for m in convs[:self.main_wgrad]}
-
-        for n in reversed(p.nodes):
-            k = n.kind
-            if k == "input" or id(n.output) not in ng:
-                continue
-            if id(n) in p.alias_nodes:
-                # concat as a view: its parts' gradients are slices of the
-                # root's buffer, which the consumers accumulated into
-                r = p.alias[id(n.output)][0]
-                if r in ginit:
-                    dB = p.tmp[("ga", r)]
-                    for t in n.inputs:
-                        if id(t) in ng and id(t) not in grad:
-                            off = p.alias[id(t)][1]
-                            grad[id(t)] = dB[..., off:off + p.shapes[id(t)][3]]
-                continue
-            if k == "xent":
-                contribute_alias(n.inputs[0], n.dlogits)
-                continue
-            dy = grad.get(id(n.output))
-            if dy is None:
-                continue          # output does not reach the loss
-            if k == "conv":
-                x = n.inputs[0]
-                yb = buf[id(n.output)]
-                dz = dy
-                fused_db = None
-                if not n.relu and n.kp_val is not None and n.kp_val < 1.0 and id(n) not in p.drop_folded:
-                    # dropout applied in the forward epilogue, no ReLU: re-draw its mask
-                    dz = p.tmp.get(("dz", id(n.output)))
-                    if dz is None:
-                        dz = torch.zeros_like(yb)
-                        p.tmp[("dz", id(n.output))] = dz
-                    ops.dropout_bwd_ch(dy, dz, n.desc.k_valid, n.kp_val, n.seed_val)
-                    if n.bias is not None:
-                        fused_db = gdst(n.bias.var_name)
-                elif id(n) in p.mask_fuse or (n.bias is not None and not n.relu):
-                    # gradient arrives masked (or there is no ReLU): BiasAddGrad is
-                    # summed by the filter-gradient launch below
-                    if n.bias is not None:
-                        fused_db = gdst(n.bias.var_name)
-                elif n.relu or n.bias is not None:
-                    scale = 1.0 / n.kp_val if (n.kp_val is not None and n.kp_val < 1.0) else 1.0
-                    dz = p.tmp.get(("dz", id(n.output)))
-                    if dz is None:
-                        dz = torch.zeros_like(yb)
-                        p.tmp[("dz", id(n.output))] = dz
-                    db = gdst(n.bias.var_name) if n.bias is not None else None
-                    K = n.desc.k_valid
-                    self._bias_relu_bwd(dy, yb if n.relu else None, dz, db, K, n.relu, scale)
-                dx = None
-                dx_base = None
-                unpool = None       # tests: (full-res gradient, switches, relu) of a fused MaxPoolGrad
-                bnb = None          # tests: record of a BatchNorm backward run in this conv's dgrad epilogue
-                pro = getattr(n, "pro", None)
-                if (id(x) in ng and pro is not None and self.fuse_bn_bwd and id(pro.inputs[0]) in ng
-                        and ops.conv_bwd_data_bn_workspace(n.desc) > 0):
-                    # input gradient carried through the folded BatchNorm(+ReLU)
-                    # backward in the same launch: the BN node's own backward is
-                    # skipped (its output gradient is never materialised)
-                    xb = pro.inputs[0]
-                    if id(xb) in p.alias:
-                        dxb, accf = adest(xb)
-                        acc = None
-                    else:
-                        (dxb, acc), accf = dest(xb), False
-                    gn, bn_ = pro.gamma.var_name, pro.beta.var_name
-                    if self.capture is not None:
-                        bnb = {"xb": buf[id(xb)], "gamma": gn, "beta": bn_, "eps": pro.eps, "relu": pro.relu,
-                               "base": dxb.clone() if accf else None, "drop": None, "folded": True}
-                    if bn_defer is not None:
-                        part = bn_part(n)
-                        self._timed(n.desc, ops.OP_BWD_DATA_BN, ops.conv2d_bwd_data_bn_part, n.desc, dz,
-                                    store.packed[(n.w.var_name, ops.PACK_HWIO)][0], buf[id(xb)], store.param(gn),
-                                    store.param(bn_), dxb, part, pro.eps, pro.relu, accf)
-                        bn_defer.append(((part, ops.conv_bwd_data_bn_part_rows(n.desc), n.desc.C, n.desc.c_valid,
-                                          pro.eps, gdst(gn), gdst(bn_)), [gn, bn_]))
-                    else:
-                        self._timed(n.desc, ops.OP_BWD_DATA_BN, ops.conv2d_bwd_data_bn, n.desc, dz,
-                                    store.packed[(n.w.var_name, ops.PACK_HWIO)][0], buf[id(xb)], store.param(gn),
-                                    store.param(bn_), dxb, gdst(gn), gdst(bn_), pro.eps, pro.relu, accf, ws)
-                    if bnb is not None:
-                        bnb["dxb"] = dxb.clone()
-                        bnb["kernel"] = ops.conv_kernel_info(n.desc, ops.OP_BWD_DATA_BN)[0]
-                    done(dxb, acc)
-                    if bn_defer is None:
-                        self._grad_ready([gn, bn_])
-                elif (id(x) in ng and id(n) in p.bn_before and self.fuse_bn_bwd
-                      and id(p.bn_before[id(n)].inputs[0]) in ng and id(p.bn_before[id(n)].inputs[0]) not in p.alias
-                      and id(p.bn_before[id(n)].inputs[0]) not in grad
-                      and ops.conv_bwd_data_bn_workspace(n.desc) > 0):
-                    # growth conv: its input gradient continues through the BN
-                    # (+ the dropout before it) that produced its input
-                    b = p.bn_before[id(n)]
-                    xb = b.inputs[0]
-                    dxb, acc = dest(xb)
-                    c1 = p.drop_fold.get(id(b))
-                    drop = (c1.kp_val, c1.seed_val) if (c1 is not None and c1.kp_val is not None
-                                                         and c1.kp_val < 1.0) else None
-                    gn, bn_ = b.gamma.var_name, b.beta.var_name
-                    if bn_defer is not None:
-                        part = bn_part(n)
-                        self._timed(n.desc, ops.OP_BWD_DATA_BN, ops.conv2d_bwd_data_bn_part, n.desc, dz,
-                                    store.packed[(n.w.var_name, ops.PACK_HWIO)][0], buf[id(xb)], store.param(gn),
-                                    store.param(bn_), dxb, part, b.eps, b.relu, False, None, drop)
-                        bn_defer.append(((part, ops.conv_bwd_data_bn_part_rows(n.desc), n.desc.C, n.desc.c_valid,
-                                          b.eps, gdst(gn), gdst(bn_)), [gn, bn_]))
-                    else:
-                        self._timed(n.desc, ops.OP_BWD_DATA_BN, ops.conv2d_bwd_data_bn, n.desc, dz,
-                                    store.packed[(n.w.var_name, ops.PACK_HWIO)][0], buf[id(xb)], store.param(gn),
-                                    store.param(bn_), dxb, gdst(gn), gdst(bn_), b.eps, b.relu, False, ws,
-                                    None, drop)
-                    if self.capture is not None:
-                        bnb = {"xb": buf[id(xb)], "gamma": gn, "beta": bn_, "eps": b.eps, "relu": b.relu,
-                               "base": None, "drop": drop, "folded": False, "dxb": dxb.clone(),
-                               "kernel": ops.conv_kernel_info(n.desc, ops.OP_BWD_DATA_BN)[0]}
-                    done(dxb, acc)
-                    if bn_defer is None:
-                        self._grad_ready([gn, bn_])
-                elif id(n) in p.unpool_fuse:
-                    # input gradient continued through the MaxPoolGrad of the pool
-                    # before this conv (and its input's ReluGrad): written at the
-                    # pool input's resolution; the pooled gradient of the pool's
-                    # other consumers (done earlier in backward) is the residual
-                    m = p.unpool_fuse[id(n)]
-                    xf = m.inputs[0]
-                    dxf, accf = dest(xf)
-                    prod = p.producer.get(id(xf))
-                    res = grad.get(id(x))
-                    if res is not None and self.capture is not None:
-                        dx_base = res.clone()
-                    self._timed(n.desc, ops.OP_BWD_DATA, ops.conv2d_bwd_data_unpool, n.desc, dz,
-                                store.packed[(n.w.var_name, ops.PACK_HWIO)][0], p.pool_idx[id(m)], dxf,
-                                prod is not None and id(prod) in p.mask_fuse, res, ws)
-                    if self.capture is not None:
-                        unpool = (dxf.clone(), p.pool_idx[id(m)], prod is not None and id(prod) in p.mask_fuse)
-                    done(dxf, accf)
-                elif id(x) in ng and id(x) in p.alias:
-                    # the input is an aliased concat root (FC-DenseNet decoder
-                    # concat views): the input gradient lands in the shared
-                    # gradient buffer -- whole (first write) or accumulated
-                    # in the epilogue
-                    dx, accf = adest(x)
-                    if accf and self.capture is not None:
-                        dx_base = dx.clone()
-                    self._timed(n.desc, ops.OP_BWD_DATA, ops.conv2d_bwd_data, n.desc, dz,
-                                store.packed[(n.w.var_name, ops.PACK_HWIO)][0], dx, ws, None,
-                                ops.epilogue(residual=dx) if accf else None)
-                elif id(x) in ng:
-                    dx, acc = dest(x)
-                    mepi = self._mask_epi(p, x)
-                    if acc is not None and mepi is None and self.fuse_grad_sum:
-                        # a further consumer's contribution: accumulated in the
-                        # epilogue, in place (residual = the gradient so far)
-                        if self.capture is not None:
-                            # tests: the sum before this launch (an extra copy on
-                            # the stream; the launch plan is unchanged)
-                            dx_base = acc.clone()
-                        self._timed(n.desc, ops.OP_BWD_DATA, ops.conv2d_bwd_data, n.desc, dz,
-                                    store.packed[(n.w.var_name, ops.PACK_HWIO)][0], acc, ws, None,
-                                    ops.epilogue(residual=acc))
-                        dx = acc
-                    elif mepi is not None and acc is None and id(n) in p.bits_dgrad:
-                        # the ReluGrad mask from the producer's bits (planner._plan_relu_bits)
-                        self._timed(n.desc, ops.OP_BWD_DATA, ops.conv2d_bwd_data_bits, n.desc, dz,
-                                    store.packed[(n.w.var_name, ops.PACK_HWIO)][0],
-                                    p.mask_bits[id(p.producer[id(x)])], dx, mepi.mask_scale, ws)
-                        done(dx, acc)
-                    else:
-                        self._timed(n.desc, ops.OP_BWD_DATA, ops.conv2d_bwd_data, n.desc, dz,
-                                    store.packed[(n.w.var_name, ops.PACK_HWIO)][0], dx, ws, None, mepi)
-                        done(dx, acc)
-                if self.capture is not None:
-                    # tests: the buffers of this layer's three kernels (they persist
-                    # after the step; dx before any accumulation of later consumers,
-                    # or -- accumulated in the epilogue -- with dx_base, the sum it
-                    # was added to; None when it went straight through a folded BN
-                    # backward)
-                    mask = self._mask_epi(p, x) if dx is not None else None
-                    self.capture.append({"kind": "conv", "name": n.w.var_name, "bias": getattr(n.bias, "var_name", None),
-                                         "x": buf[id(x)] if pro is None else buf[id(pro.inputs[0])],
-                                         "pro": None if pro is None else (pro.gamma.var_name, pro.beta.var_name,
-                                                                          pro.eps, pro.relu),
-                                         "y": buf[id(n.output)], "dz": dz,
-                                         # MaxPool fused into the forward: (pooled map, switches)
-                                         "pool": ((buf[id(p.pool_fuse[id(n)].output)],
-                                                   p.pool_idx.get(id(p.pool_fuse[id(n)])))
-                                                  if id(n) in p.pool_fuse else None),
-                                         # a copy: later consumers may accumulate into the buffer
-                                         "dx": None if dx is None else dx.clone(), "dx_base": dx_base,
-                                         "unpool": unpool,
-                                         "dx_masked": mask is not None,
-                                         "mask_scale": (mask.mask_scale if mask is not None else 1.0),
-                                         "relu": n.relu, "keep_prob": n.kp_val, "seed": n.seed_val,
-                                         # input gradient through a BatchNorm(+ReLU) backward in
-                                         # the dgrad epilogue (igemm_nt2_bn / conv_res16c_bn)
-                                         "bn_bwd": bnb,
-                                         "fused_adam": False, "desc": n.desc,
-                                         "stride": n.stride, "dilation": n.dilation, "dilation_hw": n.dilation_hw,
-                                         "padding": n.padding})
-                want_w = n.w.var_name in p.var_set
-                want_b = n.bias is not None and n.bias.var_name in p.var_set
-                gw = store.grad(n.w.var_name) if want_w else self._scratch_grad(p, n.w)
-                if not (want_w or want_b):
-                    pass          # frozen layer (outside var_list): no filter gradient
-                elif getattr(n, "pro", None) is not None:
-                    # input relu(BN(x)) recomputed from x while staging (folded BatchNorm);
-                    # on the side stream beside the input-gradient chain, as below
-                    b = n.pro
-                    side = self._wgrad_side(p, n)
-                    with self._beside(side):
-                        self._timed(n.desc, ops.OP_BWD_FILTER_PRO, ops.conv2d_bwd_filter_pro, n.desc,
-                                    buf[id(b.inputs[0])], self._prologue(b), dz, gw,
-                                    self._node_ws(p, n) if side is not None else ws, None, fused_db)
-                elif self._fused is not None and id(n) in p.adam_fusable and want_w:
-                    # Conv2DBackpropFilter + AdamOptimizer on the filter in one launch
-                    opt, gs, fdone = self._fused
-                    wn = n.w.var_name
-                    side = self._wgrad_side(p, n, level=2)
-
-                    def launch_fused(n=n, x=x, dz=dz, wn=wn, fused_db=fused_db, side=side, opt=opt, gs=gs):
-                        # on the side stream too: its input gradient (the only reader of the
-                        # packed copies it rewrites) is already enqueued on the compute stream
-                        with self._beside(side):
-                            self._timed(n.desc, ops.OP_BWD_FILTER, ops.conv2d_bwd_filter_adam, n.desc, buf[id(x)],
-                                        dz, store.param(wn), store.adam_m(wn), store.adam_v(wn), opt.lr, store.step,
-                                        opt.beta1, opt.beta2, opt.epsilon, gs, store.packed.get((wn, ops.PACK_HWIO)),
-                                        store.packed.get((wn, ops.PACK_KRSC)),
-                                        store.grad(wn) if self.store_fused_grads else None, fused_db,
-                                        self._node_ws(p, n) if side is not None else ws)
-                    if side is not None and self.fused_delay > 0:
-                        # issued after the next `fused_delay` side-stream filter gradients, so
-                        # the HBM-bound update does not starve the input-gradient chain early on
-                        self._pending_fused.append([self.fused_delay, launch_fused])
-                    else:
-                        launch_fused()
-                    fdone.add(wn)
-                    if self.capture is not None:
-                        self.capture[-1]["fused_adam"] = True
-                elif self._red is not None and self.side_wgrad >= 1 and id(n) not in main_wg:
-                    # the whole filter gradient (kernel + split-K reduction) on the
-                    # side stream, beside the input-gradient chain: every operand
-                    # (x, dz, the per-node workspace) stays untouched until the
-                    # join before Adam
-                    wsb = p.wg_ws[id(n)]
-                    with self._beside(self._red[0]):
-                        tok = self._timed(n.desc, ops.OP_BWD_FILTER, ops.conv2d_bwd_filter_begin, n.desc, buf[id(x)],
-                                          dz, gw, wsb, fused_db)
-                        ops.conv2d_bwd_filter_end(tok, gw, wsb, fused_db)
-                    self._tick_fused()
-                elif self._red is not None and id(n) not in main_wg:
-                    # kernel now, its split-K reduction on the side stream
-                    side, main = self._red
-                    wsb = p.wg_ws[id(n)]
-                    tok = self._timed(n.desc, ops.OP_BWD_FILTER, ops.conv2d_bwd_filter_begin, n.desc, buf[id(x)],
-                                      dz, gw, wsb, fused_db)
-                    if tok[1][0] > 1:
-                        ev = torch.cuda.Event()
-                        ev.record(main)
-                        side.wait_event(ev)
-                        ops.conv2d_bwd_filter_end(tok, gw, wsb, fused_db, stream=side)
-                else:
-                    self._timed(n.desc, ops.OP_BWD_FILTER, ops.conv2d_bwd_filter, n.desc, buf[id(x)], dz,
-                                gw, ws, None, fused_db)
-                self._grad_ready([n.w.var_name] + ([n.bias.var_name] if n.bias is not None else []))
-            elif k == "tconv":
-                x = n.inputs[0]
-                if n.residual is not None:
-                    contribute_alias(n.residual, dy)
-                if id(x) in ng and id(x) in p.alias:
-                    # the input is an aliased concat root (decoder concat views)
-                    dx, accf = adest(x)
-                    self._timed(n.desc, ops.OP_TBWD_DATA, ops.tconv2d_bwd_data, n.desc, dy,
-                                store.packed[(n.w.var_name, ops.PACK_TCONV_BWD)][0], dx, ws, None,
-                                ops.epilogue(residual=dx) if accf else None)
-                elif id(x) in ng:
-                    dx, acc = dest(x)
-                    self._timed(n.desc, ops.OP_TBWD_DATA, ops.tconv2d_bwd_data, n.desc, dy,
-                                store.packed[(n.w.var_name, ops.PACK_TCONV_BWD)][0], dx, ws, None,
-                                self._mask_epi(p, x))
-                    done(dx, acc)
-                want_w = n.w.var_name in p.var_set
-                want_b = n.bias is not None and n.bias.var_name in p.var_set
-                if want_w or want_b:
-                    # on the side stream beside the input-gradient chain (as the conv filter gradients)
-                    side = self._wgrad_side(p, n)
-                    with self._beside(side):
-                        self._timed(n.desc, ops.OP_TBWD_FILTER, ops.tconv2d_bwd_filter, n.desc, buf[id(x)], dy,
-                                    store.grad(n.w.var_name) if want_w else self._scratch_grad(p, n.w),
-                                    self._node_ws(p, n) if side is not None else ws, None,
-                                    gdst(n.bias.var_name) if n.bias is not None else None)
-                self._grad_ready([n.w.var_name] + ([n.bias.var_name] if n.bias is not None else []))
-            elif k == "MaxPool":
-                x = n.inputs[0]
-                if id(n) in p.unpool_pools:
-                    continue          # done in the consuming conv's input-gradient epilogue
-                if id(x) in ng:
-                    dx, acc = dest(x)
-                    prod = p.producer.get(id(x))
-                    relu = prod is not None and id(prod) in p.mask_fuse
-                    idx = p.pool_idx.get(id(n))
-                    if idx is not None:
-                        ops.maxpool2x2_bwd_argmax(idx, dy, dx, relu_mask=relu)
-                    else:
-                        ops.maxpool2x2_bwd(buf[id(x)], buf[id(n.output)], dy, dx, relu_mask=relu)
-                    done(dx, acc)
-            elif k == "AvgPool":
-                x = n.inputs[0]
-                if id(x) in ng:
-                    dx, acc = dest(x)
-                    ops.avgpool2x2_bwd(dy, dx)
-                    done(dx, acc)
-            elif k == "Add":
-                for t in n.inputs:
-                    contribute_alias(t, dy)
-            elif k == "ConcatV2":
-                parts = []
-                for t in n.inputs:
-                    if id(t) not in ng:
-                        # still consume its channel range: a zero-width part is not allowed,
-                        # so write into a scratch gradient that nobody reads
-                        g = p.tmp.get(("cz", id(t)))
-                        if g is None:
-                            g = torch.zeros_like(buf[id(t)])
-                            p.tmp[("cz", id(t))] = g
-                        parts.append((g, p.shapes[id(t)][3], False))
-                        continue
-                    if id(t) in p.alias:
-                        v, accf = adest(t)
-                        parts.append((v, p.shapes[id(t)][3], accf))
-                    elif id(t) in grad:
-                        parts.append((grad[id(t)], p.shapes[id(t)][3], True))
-                    else:
-                        g = p.tmp.get(("g", id(t)))
-                        if g is None:
-                            g = torch.zeros_like(buf[id(t)])
-                            p.tmp[("g", id(t))] = g
-                        grad[id(t)] = g
-                        parts.append((g, p.shapes[id(t)][3], False))
-                ops.concat_bwd(dy, parts)
-            elif k == "bn":
-                x = n.inputs[0]
-                C = p.shapes[id(x)][3]
-                if id(x) in p.alias:
-                    dx, accf = adest(x)
-                    acc = None
-                else:
-                    (dx, acc), accf = dest(x), False
-                drop = None
-                c = p.drop_fold.get(id(n))
-                if c is not None and c.kp_val is not None and c.kp_val < 1.0:
-                    if accf or acc is not None:
-                        raise RuntimeError(f"{n.ops[0].name}: folded dropout gradient needs a sole reader")
-                    drop = (c.kp_val, c.seed_val, c.desc.k_valid)
-                ops.bn_relu_bwd(buf[id(x)], buf[id(n.output)], dy, dx, store.param(n.gamma.var_name),
-                                gdst(n.gamma.var_name), gdst(n.beta.var_name), C, n.relu,
-                                n.eps, ws, accumulate=accf, beta=store.param(n.beta.var_name), dropout=drop)
-                done(dx, acc)
-                self._grad_ready([n.gamma.var_name, n.beta.var_name])
-            elif k == "Relu":
-                x = n.inputs[0]
-                dx, acc = dest(x)
-                self._bias_relu_bwd(dy, buf[id(n.output)], dx, None, p.shapes[id(x)][3], True, 1.0)
-                done(dx, acc)
-            elif k == "Dropout":
-                x = n.inputs[0]
-                dx, acc = dest(x)
-                if n.kp_val < 1.0:
-                    ops.dropout_fwd(dy, dx, n.kp_val, n.seed_val)
-                else:
-                    ops.copy_channels(dy, dx)
-                done(dx, acc)
-            elif k == "GlobalAvgPool":
-                x = n.inputs[0]
-                if id(x) in ng:
-                    dx, acc = dest(x)
-                    xs = buf[id(x)]
-                    ops.spatial_broadcast(dy, dx, 1.0 / (xs.shape[1] * xs.shape[2]))
-                    done(dx, acc)
-            elif k == "ExpandDims" and len(p.shapes[id(n.output)]) == 4 and len(p.shapes[id(n.inputs[0])]) == 4:
-                contribute_alias(n.inputs[0], dy)          # global-average-pool chain: same buffer
-            elif k == "ResizeBilinear" and buf[id(n.inputs[0])].shape[1] == 1 and buf[id(n.inputs[0])].shape[2] == 1:
-                x = n.inputs[0]
-                if id(x) in ng:                            # 1x1 -> HxW broadcast: gradient = spatial sum
-                    dx, acc = dest(x)
-                    ops.spatial_reduce(dy, dx, 1.0, self.ws)
-                    done(dx, acc)
-            elif k == "ResizeBilinear":
-                # align_corners bilinear: fp32 scatter-add, then cast to the compute dtype
-                x = n.inputs[0]
-                if id(x) in ng:
-                    dx, acc = dest(x)
-                    g32 = p.tmp.get(("rb32", id(x)))
-                    if g32 is None:
-                        g32 = torch.zeros(dx.shape, dtype=torch.float32, device=self.device)
-                        p.tmp[("rb32", id(x))] = g32
-                    ops.resize_bilinear_bwd(dy, g32)
-                    ops.cast(g32, dx)
-                    done(dx, acc)
-            elif k == "Softmax":
-                raise NotImplementedError("gradient of tf.nn.softmax: the reference uses it for evaluation only "
-                                          "(Network/utils/utils.py:54); train on softmax_cross_entropy_with_logits")
-            elif k in ("ArgMax", "ExpandDims"):
-                continue
-            else:
-                raise NotImplementedError(f"backward of {k}")
-        if bn_defer:
-            # every deferred dgamma / dbeta in two launches (the same sums as
-            # each launch's own finish); the segment table is built once per plan
-            segs = [s for s, _ in bn_defer]
-            key = tuple((s[0].data_ptr(), int(s[1]), s[5].data_ptr()) for s in segs)
-            batch = getattr(p, "bn_batch", None)
-            if batch is None or batch.key != key:
-                batch = ops.BnFinishBatch(segs, self.device)
-                p.bn_batch = batch
-            batch.run()
-            self._grad_ready([nm for _, names in bn_defer for nm in names])
-
-    def _grads_finite(self):
-        """All gradients finite (every rank's, under data parallelism)?  One
-        device-to-host read per step on the loss-scaled path."""
-        if self._finite_flag is None:
-            self._finite_flag = torch.zeros(1, dtype=torch.int32, device=self.device)
-        ops.check_finite(self.store.grads, self._finite_flag)
-        if self._dpa is not None:
-            import torch.distributed as dist
-            dist.all_reduce(self._finite_flag, op=dist.ReduceOp.MAX, group=self.dp.group)
-        return int(self._finite_flag.item()) == 0
-
-    def _prologue(self, b):
-        st = self.store
-        return ops.prologue(st.param(b.gamma.var_name), st.param(b.beta.var_name), b.eps, b.relu)
-
-    def _scratch_grad(self, p, var):
-        """fp32 gradient sink for a filter outside var_list whose layer still
-        needs its bias gradient (the filter-gradient launch sums it)."""
-        t = p.tmp.get(("wscratch", var.var_name))
-        if t is None:
-            t = torch.zeros(tuple(var.shape), dtype=torch.float32, device=self.device)
-            p.tmp[("wscratch", var.var_name)] = t
-        return t
 
     def _check_bn_stats(self, p):
         """The kernels fold BatchNorm's frozen statistics as mean 0 / variance
@@ -1494,10 +825,6 @@ class Session(PlanMixin, StreamMixin):
                 raise NotImplementedError(f"{v.var_name}: BatchNormalization moving statistics other than "
                                           f"the frozen (0, 1) of the reference are not on the hot path")
         self._bn_checked = store.aux_version
-
-    def _bias_relu_bwd(self, dy, y, dz, dbias, k_valid, relu, scale):
-        # with TF1 dropout fused after the relu: dz = dy * (y > 0) / keep_prob
-        ops.bias_relu_bwd(dy, y, dz, dbias, k_valid, relu, self.ws, scale=scale)
 
     def close(self):
         self.plans = {}

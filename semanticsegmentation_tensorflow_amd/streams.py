@@ -1,8 +1,9 @@
 """Stream scheduling of a Session step (mixin): the side stream that runs the
 filter gradients and their split-K reductions beside the input-gradient chain,
 the deferred fused filter-gradient + Adam launches, per-launch HIP-event
-timing, and the overlapped per-layer optimizer.  Split out of session.py;
-`Session` inherits these methods unchanged."""
+timing, and the overlapped per-layer optimizer.  Split out of session.py (as
+planner.py and forward.py / backward.py, whose launches go through these
+helpers); `Session` inherits these methods."""
 from __future__ import annotations
 
 import contextlib
