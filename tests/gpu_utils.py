@@ -31,6 +31,39 @@ def rel_err(a, b):
     return (a - b).abs().max().item() / max(b.abs().max().item(), 1e-30)
 
 
+_INT_OF = {torch.float32: torch.int32, torch.bfloat16: torch.int16, torch.float16: torch.int16}
+
+
+def assert_bits_equal(got, ref, what=""):
+    """Bit for bit (so -0.0 != +0.0); NaNs compared by position, not by payload."""
+    got, ref = got.detach().cpu().reshape(-1), ref.detach().cpu().reshape(-1)
+    assert got.dtype == ref.dtype and got.shape == ref.shape, f"{what}: {got.dtype}{tuple(got.shape)} vs " \
+                                                              f"{ref.dtype}{tuple(ref.shape)}"
+    gn, rn = torch.isnan(got), torch.isnan(ref)
+    assert torch.equal(gn, rn), f"{what}: NaN positions differ ({int(gn.sum())} vs {int(rn.sum())})"
+    it = _INT_OF[got.dtype]
+    bad = ((got.view(it) != ref.view(it)) & ~gn).nonzero().reshape(-1)
+    assert bad.numel() == 0, (f"{what}: {bad.numel()} of {got.numel()} elements differ, first at {bad[0].item()}: "
+                              f"{got[bad[0]].item()!r} vs {ref[bad[0]].item()!r}")
+
+
+def packed_ref(src, mode, dtype, a_pad=None, b_pad=None, fill=0.0):
+    """Host reference of a packed compute copy of the float master src [R,S,A,B]
+    (seg_pack_filter's layouts): modes 1 / 2 dst[r,s,a,b], modes 0 / 3
+    dst[b,r,s,a]; values src.to(dtype); the padding entries a in [A, a_pad),
+    b in [B, b_pad) hold `fill` (0.0 after a pack; whatever the copy held
+    before where a kernel leaves padding untouched)."""
+    src = src.detach().cpu()
+    R, S, A, B = src.shape
+    ap = ops.round8(A) if a_pad is None else a_pad
+    bp = ops.round8(B) if b_pad is None else b_pad
+    out = torch.full((R, S, ap, bp), fill, dtype=dtype)
+    out[:, :, :A, :B] = src.to(dtype)
+    if mode in (ops.PACK_KRSC, ops.PACK_TCONV_BWD):
+        out = out.permute(3, 0, 1, 2)
+    return out.contiguous()
+
+
 def assert_close(got, ref, dtype, what="", tol=None):
     tol = TOL[dtype] if tol is None else tol
     e = rel_err(got, ref)
