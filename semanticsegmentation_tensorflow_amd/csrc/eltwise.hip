@@ -393,7 +393,13 @@ template <typename T>
 __global__ void dropout_k(const T* __restrict__ x, T* __restrict__ y, long n, float kp, uint64_t seed) {
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
         const float u = seg_uniform(seed, (uint64_t)i);
-        y[i] = from_f32<T>((to_f32(x[i]) * (1.f / kp)) * floorf(kp + u));
+        // the fp32 product is pinned before the 16-bit rounding (as in resize_fwd_k): hipcc
+        // otherwise folds the last multiply and the fp16 conversion of the loop's tail
+        // elements into v_fma_mixlo_f16 with a +0 addend, and a dropped negative x came out
+        // +0 there but -0 (TF's x / kp * 0) in the packed main loop
+        float r = (to_f32(x[i]) * (1.f / kp)) * floorf(kp + u);
+        asm volatile("" : "+v"(r));
+        y[i] = from_f32<T>(r);
     }
 }
 
@@ -811,6 +817,13 @@ __global__ __launch_bounds__(256) void part_rows_reduce_k(const float* __restric
 template <typename T>
 __global__ __launch_bounds__(256) void resize_fwd_k(const T* __restrict__ x, T* __restrict__ y, int N, int H, int W,
                                                     int C, int OH, int OW) {
+    // The source position is TF's float32 arithmetic, src = float(o) * scale
+    // rounded to fp32 and only then split into floor and fraction: contracted
+    // into fma(o, scale, -floor) the fraction keeps the product's low bits and
+    // the weights drift from TF's by up to half an ulp of the position (1e-6
+    // at position 48: past the fp32 rounding of the interpolation itself).
+    // The interpolation's own fmas below are explicit.
+#pragma clang fp contract(off)
     const float sh = OH > 1 ? (float)(H - 1) / (float)(OH - 1) : 0.f;
     const float sw = OW > 1 ? (float)(W - 1) / (float)(OW - 1) : 0.f;
     const int row = blockIdx.x;                   // n * OH + oy
@@ -850,6 +863,7 @@ __global__ __launch_bounds__(256) void resize_fwd_k(const T* __restrict__ x, T* 
 template <typename T>
 __global__ __launch_bounds__(256) void resize_fwd8_k(const T* __restrict__ x, T* __restrict__ y, int N, int H, int W,
                                                      int C, int OH, int OW) {
+#pragma clang fp contract(off)
     const float sh = OH > 1 ? (float)(H - 1) / (float)(OH - 1) : 0.f;
     const float sw = OW > 1 ? (float)(W - 1) / (float)(OW - 1) : 0.f;
     const int row = blockIdx.x;                   // n * OH + oy
@@ -898,6 +912,7 @@ __device__ __forceinline__ void resize_src_range(int i, float s, int n_out, int&
 }
 
 __device__ __forceinline__ float resize_weight(int o, int i, float s, int n_in) {
+#pragma clang fp contract(off)   // TF's float32 position: see resize_fwd_k
     const float f = o * s;
     const int a = (int)floorf(f);
     const int b = min(a + 1, n_in - 1);
@@ -910,6 +925,7 @@ __device__ __forceinline__ float resize_weight(int o, int i, float s, int n_in) 
 template <typename T>
 __global__ __launch_bounds__(256) void resize_bwd_k(const T* __restrict__ dy, float* __restrict__ dx, int N, int H,
                                                     int W, int C, int OH, int OW) {
+#pragma clang fp contract(off)
     const float sh = OH > 1 ? (float)(H - 1) / (float)(OH - 1) : 0.f;
     const float sw = OW > 1 ? (float)(W - 1) / (float)(OW - 1) : 0.f;
     const int row = blockIdx.x;                   // n * H + y
@@ -942,6 +958,7 @@ __global__ __launch_bounds__(256) void resize_bwd_k(const T* __restrict__ dy, fl
 template <typename T>
 __global__ __launch_bounds__(256) void resize_bwd8_k(const T* __restrict__ dy, float* __restrict__ dx, int N, int H,
                                                      int W, int C, int OH, int OW) {
+#pragma clang fp contract(off)
     const float sh = OH > 1 ? (float)(H - 1) / (float)(OH - 1) : 0.f;
     const float sw = OW > 1 ? (float)(W - 1) / (float)(OW - 1) : 0.f;
     const int row = blockIdx.x;                   // n * H + y

@@ -641,6 +641,13 @@ def dropout_fwd(x, y, keep_prob, seed, stream=None):
     return y
 
 
+def dropout_bwd(dy, dx, keep_prob, seed, stream=None):
+    """Gradient of dropout_fwd with the same seed: the same mask and 1/keep_prob scale."""
+    check(_lib.lib().seg_dropout_bwd(ptr(dy), ptr(dx), dy.numel(), float(keep_prob), int(seed),
+                                     seg_dtype(dy), stream_ptr(stream)), "dropout_grad")
+    return dx
+
+
 def dropout_bwd_ch(dy, dz, c_valid, keep_prob, seed, stream=None):
     """Gradient of a conv-epilogue dropout (counter p * c_valid + c)."""
     C = dy.shape[-1]

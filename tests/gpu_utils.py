@@ -47,6 +47,65 @@ def assert_bits_equal(got, ref, what=""):
                               f"{got[bad[0]].item()!r} vs {ref[bad[0]].item()!r}")
 
 
+# unit roundoffs: fp32 arithmetic (U) and the storage formats (U_DT)
+U = 2.0 ** -24
+U_DT = {torch.float32: 2.0 ** -24, torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11}
+
+
+def assert_within(got, ref, bound, what=""):
+    """|got - ref| <= bound element by element (float64 tensors of one shape, on
+    any one device); a NaN / Inf in got where ref is finite fails."""
+    got, ref, bound = got.double(), ref.double(), bound.double()
+    assert got.shape == ref.shape == bound.shape, f"{what}: {tuple(got.shape)} vs {tuple(ref.shape)}"
+    err = (got - ref).abs()
+    bad = ~(err <= bound)                       # also true for NaN
+    n = int(bad.sum())
+    if n:
+        i = int(bad.reshape(-1).nonzero()[0])
+        g, r, b = got.reshape(-1)[i].item(), ref.reshape(-1)[i].item(), bound.reshape(-1)[i].item()
+        raise AssertionError(f"{what}: {n} of {got.numel()} elements out of bound, first at {i}: "
+                             f"{g!r} vs {r!r} (|diff| {abs(g - r):.3e} > {b:.3e})")
+    big = err / bound.clamp_min(1e-300)
+    return float(big[bound > 0].max()) if bool((bound > 0).any()) else 0.0
+
+
+def storage_bound(ref, dtype, fp32_term):
+    """Rule for a result computed in fp32 and stored in `dtype`: the fp32 error
+    term plus one rounding of the (possibly double-rounded) stored value."""
+    return U_DT[dtype] * ref.abs() + fp32_term
+
+
+def assert_surroundings(view, junk=50.0, what=""):
+    """A channel-slice view's buffer still holds `junk` everywhere outside the view."""
+    base = view._base
+    assert base is not None and base.shape[:-1] == view.shape[:-1]
+    lead = view.storage_offset() - base.storage_offset()
+    cp = view.shape[-1]
+    outside = torch.cat([base[..., :lead], base[..., lead + cp:]], dim=-1)
+    assert bool((outside == junk).all()), f"{what}: bytes around the view changed"
+
+
+def randn_normal(shape, gen, dtype, scale=1.0, floor=2.0 ** -6):
+    """scale * randn rounded through `dtype`, magnitudes floored at `floor`: the
+    values and their small multiples (x 0.25, x 1.25) stay normal in fp16."""
+    x = torch.randn(shape, generator=gen, dtype=torch.float64) * scale
+    x = torch.where(x.abs() < floor, torch.where(x < 0, -floor, floor).to(torch.float64), x)
+    return rnd(x, dtype)
+
+
+def nan_like_view(shape, dtype, dev, make_view):
+    """An output buffer prefilled with NaN: dense, or (make_view: a function
+    float64 NHWC -> device view) a channel-slice view."""
+    full = torch.full(shape, float("nan"), dtype=torch.float64)
+    return make_view(full) if make_view is not None else full.to(dtype).to(dev)
+
+
+def tile_rows(t, P):
+    """The first P rows of t [p0, ...] repeated along dim 0."""
+    reps = (P + t.shape[0] - 1) // t.shape[0]
+    return t.repeat(reps, *([1] * (t.dim() - 1)))[:P]
+
+
 def packed_ref(src, mode, dtype, a_pad=None, b_pad=None, fill=0.0):
     """Host reference of a packed compute copy of the float master src [R,S,A,B]
     (seg_pack_filter's layouts): modes 1 / 2 dst[r,s,a,b], modes 0 / 3
