@@ -621,6 +621,7 @@ const Knob* find_knob(const char* name) {
         {"tn3_adam_abl", &seg::KnobSet::tn3_adam_abl, 0, 31, 1, {}},
         {"wgrad_abl", &seg::KnobSet::wgrad_abl, 0, 3, 1, {}},
         {"nt2_ablate", &seg::KnobSet::nt2_ablate, 0, 19, 1, {}},
+        {"res64_abl", &seg::KnobSet::res64_abl, 0, 5, 1, {}},
 #endif
     };
     for (const Knob& k : knobs)

@@ -26,6 +26,8 @@
 // Covers Conv2D fwd and Conv2DBackpropInput of stride-1 convs (dilation any)
 // with C % 64 == 0 -- conv1_2 ... conv5_3 of FCN (Network/model/FCN.py:55-99)
 // and the FC-DenseNet 3x3 layers.
+#include <type_traits>
+
 #include "common.h"
 #include "igemm.h"
 #include "ldsdma.h"
@@ -1236,10 +1238,20 @@ __global__ __launch_bounds__(512, NB == 16 ? (DMA ? 4 : 2) : 1) void conv_res64(
 // Given as bits (EpiParams::mask_bits, round 6: conv_c8_fwd writes them with
 // conv1_1's map) it is 8 B per pixel instead of 128: four 8-byte loads per
 // lane and tile instead of sixteen.
+// What bounds it (the ABL modes below, at conv1_2's size): the epilogue
+// phase.  Without the epilogue the launch takes ~117 us, whole ~175-185;
+// without the halo DMA ~150, and the MFMA loop with the barriers alone ~108.
+// So the epilogue's per-element work, not the depth of the halo prefetch, is
+// what to shorten first: its switches are compile-time constants for the
+// usual launches, and a pool candidate is scaled and rounded in one lane only.
 // ---------------------------------------------------------------------------
 constexpr int RPP_HS = RPP_PIECES * 8 * 128;         // 44,032 B per halo buffer
 
-template <typename T = bf16>
+// ABL (diagnostic build only, garbage results): 1 no halo DMA after the first
+// two tiles (every tile re-reads the resident buffers), 2 no MFMA, 3 no
+// epilogue (neither its arithmetic nor its stores), 4 no epilogue stores,
+// 5 = 1 + 3 (the MFMA loop and the barriers alone).
+template <typename T = bf16, int ABL = 0>
 __global__ __launch_bounds__(512, 1) void conv_res64pp(NTParams p, int tiles_x, int tiles_y, int ntiles) {
     constexpr int NB = 64, TM = 4, TN = 4;
     constexpr int BS = 9 * NB * 128;
@@ -1383,11 +1395,21 @@ __global__ __launch_bounds__(512, 1) void conv_res64pp(NTParams p, int tiles_x, 
                 for (int st = 0; st < 18; ++st) {
                     const int cur = st & 1;
                     if (st + 1 < 18) load_step(st + 1, fa[cur ^ 1], fb[cur ^ 1]);
+                    // the next step's fragment reads stay above this step's MFMAs
+                    // (left free, the scheduler sinks each read to just before its
+                    // first use and every 4 MFMAs wait out a whole LDS round trip)
+                    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int mi = 0; mi < TM; ++mi)
 #pragma unroll
-                        for (int ni = 0; ni < TN; ++ni)   // D^T[n][px] += W[n][k] X[px][k]
-                            acc[mi][ni] = mfma16x16x32<T>(fb[cur][ni], fa[cur][mi], acc[mi][ni]);
+                        for (int ni = 0; ni < TN; ++ni) {  // D^T[n][px] += W[n][k] X[px][k]
+                            if constexpr (ABL == 2) {
+                                asm volatile("" ::"v"(fb[cur][ni].x), "v"(fa[cur][mi].x), "v"(fb[cur][ni].w), "v"(fa[cur][mi].w));
+                            } else {
+                                acc[mi][ni] = mfma16x16x32<T>(fb[cur][ni], fa[cur][mi], acc[mi][ni]);
+                            }
+                        }
+                    __builtin_amdgcn_sched_barrier(0);
                 }
                 __builtin_amdgcn_s_setprio(0);
                 if (e.mask_bits) {  // channels ni * 16 + 4 fg .. + 3: one nibble per (mi, ni)
@@ -1417,8 +1439,18 @@ __global__ __launch_bounds__(512, 1) void conv_res64pp(NTParams p, int tiles_x, 
             const int img = t / tpi;
             const int rem = t - img * tpi;
             const int ty = rem / tiles_x, tx = rem - (rem / tiles_x) * tiles_x;
-            if (ph + 1 < nt) dma(tile_of(ph + 1));
-            if (e.pool_y) {    // MaxPool 2x2 / 2 fused (as conv_res64: rows 2 wm, 2 wm + 1 per wave)
+            if (ABL != 1 && ABL != 5 && ph + 1 < nt) dma(tile_of(ph + 1));
+            // The epilogue's wave-uniform switches (ReLU, dropout, mask, padded
+            // channels) are arguments of the two bodies below: the launches
+            // of the FCN step get them as compile-time constants, so their 64
+            // outputs per lane run without a scalar branch or select per element
+            // (the ablation: this phase, not the MFMA phase, sets the tile time);
+            // any other combination takes the same body with run-time flags.
+            // MaxPool 2x2 / 2 fused (as conv_res64: rows 2 wm, 2 wm + 1 per wave).
+            // A lane scales, clamps and rounds its own two candidates and takes
+            // the other column's from lane fr ^ 1, which computed them from the
+            // same accumulators with the same arithmetic.
+            auto pooled = [&](auto relu, auto allv) {
                 const int oy = ty * R64_BH + 2 * wm;
                 const int PH = p.OH >> 1, PW = p.OW >> 1;
 #pragma unroll
@@ -1433,16 +1465,15 @@ __global__ __launch_bounds__(512, 1) void conv_res64pp(NTParams p, int tiles_x, 
                         unsigned code = 0;
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
-                            const float raw[4] = {acc[mi][ni][j], dpp_swap1(acc[mi][ni][j]),
-                                                  acc[mi + 2][ni][j], dpp_swap1(acc[mi + 2][ni][j])};
-                            const bool cv = col0 + j < e.n_valid;
-                            float q[4];
+                            const bool cv = allv || col0 + j < e.n_valid;
+                            float own[2];
 #pragma unroll
-                            for (int u = 0; u < 4; ++u) {
-                                float x = raw[u] * sc4[j] + ad4[j];
-                                if (e.relu) x = fmaxf(x, 0.f);
-                                q[u] = cv ? to_f32(from_f32<T>(x)) : 0.f;
+                            for (int u = 0; u < 2; ++u) {
+                                float x = acc[mi + 2 * u][ni][j] * sc4[j] + ad4[j];
+                                if (relu) x = fmaxf(x, 0.f);
+                                own[u] = cv ? to_f32(from_f32<T>(x)) : 0.f;
                             }
+                            const float q[4] = {own[0], dpp_swap1(own[0]), own[1], dpp_swap1(own[1])};
                             unsigned a = 0;
                             float mx = q[0];
                             if (q[1] > mx) { mx = q[1]; a = 1; }
@@ -1453,12 +1484,18 @@ __global__ __launch_bounds__(512, 1) void conv_res64pp(NTParams p, int tiles_x, 
                         }
                         if ((fr & 1) || oy + 1 >= p.OH || ox + 1 >= p.OW || col0 >= p.N) continue;
                         const long pix = ((long)img * PH + (oy >> 1)) * PW + (ox >> 1);
+                        if constexpr (ABL == 4) {
+                            asm volatile("" ::"v"(o[0]), "v"(o[1]), "v"(o[2]), "v"(o[3]), "v"(code), "v"(pix));
+                            continue;
+                        }
                         *reinterpret_cast<uint2*>(reinterpret_cast<T*>(e.pool_y) + pix * e.ld_pool + col0) =
                             *reinterpret_cast<const uint2*>(o);
                         if (e.pool_idx) *reinterpret_cast<unsigned*>(e.pool_idx + pix * e.ld_idx + col0) = code;
                     }
                 }
-            } else {           // straight from registers: pixel (mi, fr), channels 4 fg .. + 3 of (ni)
+            };
+            // straight from registers: pixel (mi, fr), channels 4 fg .. + 3 of (ni)
+            auto plain = [&](auto relu, auto dropped, auto masked, auto allv) {
                 const int oy0 = ty * R64_BH, ox0 = tx * R64_BW;
 #pragma unroll
                 for (int mi = 0; mi < TM; ++mi) {
@@ -1480,21 +1517,46 @@ __global__ __launch_bounds__(512, 1) void conv_res64pp(NTParams p, int tiles_x, 
                         T o[4];
                         const f32x4 sc4 = *reinterpret_cast<const f32x4*>(etab + col0);
                         const f32x4 ad4 = *reinterpret_cast<const f32x4*>(etab + NB + col0);
-                        const SegDropRun<4> drop(e.seed, gidx + col0, e.keep_prob < 1.f);
+                        const SegDropRun<4> drop(e.seed, gidx + col0, dropped);
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
                             const int col = col0 + j;
                             float x = acc[mi][ni][j] * sc4[j] + ad4[j];
-                            if (e.relu) x = fmaxf(x, 0.f);
-                            if (e.keep_prob < 1.f) x = drop(x, e.keep_prob, j);
+                            if (relu) x = fmaxf(x, 0.f);
+                            if (dropped) x = drop(x, e.keep_prob, j);
                             x += res[j];
-                            if (e.mask || e.mask_bits) x = (mbits >> ((mi * TN + ni) * 4 + j)) & 1 ? x * e.mask_scale : 0.f;
-                            o[j] = from_f32<T>(col < e.n_valid ? x : 0.f);
+                            if (masked) x = (mbits >> ((mi * TN + ni) * 4 + j)) & 1 ? x * e.mask_scale : 0.f;
+                            o[j] = from_f32<T>(allv || col < e.n_valid ? x : 0.f);
+                        }
+                        if constexpr (ABL == 4) {
+                            asm volatile("" ::"v"(o[0]), "v"(o[1]), "v"(o[2]), "v"(o[3]), "v"(pix));
+                            continue;
                         }
                         *reinterpret_cast<uint2*>(reinterpret_cast<T*>(p.y) + img * p.y_img + pix * p.ldy + col0) =
                             *reinterpret_cast<const uint2*>(o);
                     }
                 }
+            };
+            constexpr std::true_type yes{};
+            constexpr std::false_type no{};
+            const bool relu = e.relu != 0, dropped = e.keep_prob < 1.f, masked = e.mask || e.mask_bits;
+            const bool allv = e.n_valid >= NB;
+            if constexpr (ABL == 3 || ABL == 5) {   // no epilogue: the accumulators only stay live
+#pragma unroll
+                for (int mi = 0; mi < TM; ++mi)
+#pragma unroll
+                    for (int ni = 0; ni < TN; ++ni)
+                        asm volatile("" ::"v"(acc[mi][ni][0]), "v"(acc[mi][ni][1]), "v"(acc[mi][ni][2]), "v"(acc[mi][ni][3]));
+            } else if (e.pool_y) {
+                if (relu && allv) pooled(yes, yes);             // conv1_2 + pool1
+                else pooled(relu, allv);
+            } else if (allv && !dropped && !e.residual) {
+                if (masked && !relu) plain(no, no, yes, yes);   // conv1_2's input gradient with ReluGrad
+                else if (relu && !masked) plain(yes, no, no, yes);
+                else if (!relu && !masked) plain(no, no, no, yes);
+                else plain(relu, dropped, masked, allv);
+            } else {
+                plain(relu, dropped, masked, allv);
             }
             wait_vmcnt<0>();   // this group's next halo has landed (and its stores left)
         }
@@ -2025,6 +2087,18 @@ int launch_res64(NTParams& p, int cus, hipStream_t s, int dtype) {
     }
     const int grid = std::min(ntiles, cus);
     if (g_res64_pp == 2 || (g_res64_pp == 1 && (p.epi.pool_y || p.epi.mask)) || p.epi.mask_bits) {
+#ifdef SEG_DIAG   // ablation builds (garbage results): tools/ only
+        if (g_res64_abl && dtype == SEG_BF16) {
+            switch (g_res64_abl) {
+                case 1: hipLaunchKernelGGL((conv_res64pp<bf16, 1>), dim3(grid), dim3(512), 0, s, p, tx, ty, ntiles); break;
+                case 2: hipLaunchKernelGGL((conv_res64pp<bf16, 2>), dim3(grid), dim3(512), 0, s, p, tx, ty, ntiles); break;
+                case 3: hipLaunchKernelGGL((conv_res64pp<bf16, 3>), dim3(grid), dim3(512), 0, s, p, tx, ty, ntiles); break;
+                case 4: hipLaunchKernelGGL((conv_res64pp<bf16, 4>), dim3(grid), dim3(512), 0, s, p, tx, ty, ntiles); break;
+                default: hipLaunchKernelGGL((conv_res64pp<bf16, 5>), dim3(grid), dim3(512), 0, s, p, tx, ty, ntiles); break;
+            }
+            return SEG_OK;
+        }
+#endif
         if (dtype == SEG_F16) hipLaunchKernelGGL((conv_res64pp<f16>), dim3(grid), dim3(512), 0, s, p, tx, ty, ntiles);
         else hipLaunchKernelGGL((conv_res64pp<bf16>), dim3(grid), dim3(512), 0, s, p, tx, ty, ntiles);
         return SEG_OK;

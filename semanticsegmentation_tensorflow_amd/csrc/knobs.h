@@ -26,6 +26,7 @@ namespace seg {
     X(res64, 1) \
     X(res16, 1) \
     X(res64_pp, 1) \
+    X(res64_abl, 0) \
     X(wgrad_pxs, 1) \
     X(smallc_tr, 1) \
     X(res16_dma, 1) \
@@ -87,6 +88,7 @@ KnobSet& knobs();
 #define g_res64 (::seg::knobs().res64.load(std::memory_order_relaxed))
 #define g_res16 (::seg::knobs().res16.load(std::memory_order_relaxed))   // conv_res64 with 16-wide output blocks for N <= 16
 #define g_res64_pp (::seg::knobs().res64_pp.load(std::memory_order_relaxed))
+#define g_res64_abl (::seg::knobs().res64_abl.load(std::memory_order_relaxed))   // diagnostics (garbage results), conv_res64pp: 1 no halo DMA after the first two tiles, 2 no MFMA, 3 no epilogue, 4 no epilogue stores, 5 = 1 + 3
 #define g_wgrad_pxs (::seg::knobs().wgrad_pxs.load(std::memory_order_relaxed))
 #define g_smallc_tr (::seg::knobs().smallc_tr.load(std::memory_order_relaxed))
 #define g_res16_dma (::seg::knobs().res16_dma.load(std::memory_order_relaxed))
