@@ -380,6 +380,56 @@ int seg_avgpool2x2_fwd(const void* x, void* y, int N, int H, int W, int C, int l
 int seg_avgpool2x2_bwd(const void* dy, void* dx, int N, int H, int W, int C, int ldx, int ldy,
                        int dtype, void* stream);
 
+/* ---- MaxPool / AvgPool, any window and stride, SAME or VALID ------------
+ * (Network/utils/utils.py:306-310; PSPNet50's 3x3 stride-2 max pool,
+ * Network/model/PSPNet.py:34, and its pyramid's 5x18 / 3x9 / 2x6 / 1x3 average
+ * pools with stride = window, :147-166; csrc/pool.hip).  The 2x2 entry points
+ * above stay what a 2x2 stride-2 VALID pool runs; on that geometry these give
+ * the same y and dx bit for bit. */
+typedef struct seg_pool_desc {
+    int N, H, W, C;          /* C padded, a multiple of the 16-byte chunk      */
+    int kh, kw, sh, sw;
+    int pad_top, pad_left;   /* TF SAME: total = max((out-1)*s + k - in, 0), before = total / 2 */
+    int OH, OW;
+    int ldx, ldy;            /* pixel strides: channel-slice views allowed     */
+    int kind;                /* 0 max, 1 avg                                   */
+    int dtype;
+} seg_pool_desc;
+/* TF's pooling shape function (padding: 0 = SAME, out = ceil(in / s); 1 =
+ * VALID, out = (in - k) / s + 1); ldx = ldy = C.  SEG_EINVAL, with *d
+ * untouched, for a non-positive size, a window of more than 256 elements (the
+ * switch byte cannot name the position: larger windows are what
+ * seg_spatial_reduce is for), C not a whole number of chunks, no output, or
+ * an element count >= 2^31. */
+int seg_pool_desc_init(seg_pool_desc* d, int N, int H, int W, int C, int kh, int kw,
+                       int sh, int sw, int padding, int kind, int dtype);
+/* Max: y = the maximum over the in-image elements of the window (SAME padding
+ * never wins); idx, when non-NULL (NULL for inference plans), gets one byte
+ * per pooled element, dense with row stride C, 8-byte aligned: the row-major
+ * window position r * kw + s of the FIRST maximum (seg_maxpool2x2_bwd's tie
+ * rule).  Avg: the fp32 sum divided by the number of in-image elements (TF's
+ * rule under SAME), rounded once; idx is ignored.  A descriptor that
+ * seg_pool_desc_init would refuse is refused here too, writing nothing. */
+int seg_pool2d_fwd(const seg_pool_desc* d, const void* x, void* y, uint8_t* idx, void* stream);
+/* MaxPoolGrad / AvgPoolGrad as a gather: dx [N,H,W,C] (ldx) is fully written
+ * -- the fp32 sum, rounded once, over the at most ceil(kh/sh) * ceil(kw/sw)
+ * windows containing the pixel of dy where idx names it (max; idx required)
+ * or of dy / count (avg; idx ignored); 0 where no window covers the pixel
+ * (VALID leftovers, the gaps of k < s).  No atomics, no memset.  With kh = kw
+ * = 1 and stride s this is the scatter of a subsampled gradient into the full
+ * map: the input gradient of a strided 1x1 conv (Network/model/PSPNet.py:57,
+ * :60, :83, :86, :121, :125). */
+int seg_pool2d_bwd(const seg_pool_desc* d, const uint8_t* idx, const void* dy, void* dx, void* stream);
+/* tf.pad with constant zeros on H and W (Zero_Padding, Network/utils/utils.py
+ * :325-327): y [N, H+top+bottom, W+left+right, C] is fully written, zeros in
+ * the border and a copy of x [N,H,W,C] inside.  seg_pad2d_bwd is the crop
+ * (same geometry arguments: H, W are the unpadded sizes): dx [N,H,W,C] =
+ * dy's interior.  Negative pads: SEG_EINVAL. */
+int seg_pad2d_fwd(const void* x, int ldx, void* y, int ldy, int N, int H, int W, int C,
+                  int top, int bottom, int left, int right, int dtype, void* stream);
+int seg_pad2d_bwd(const void* dy, int lddy, void* dx, int lddx, int N, int H, int W, int C,
+                  int top, int bottom, int left, int right, int dtype, void* stream);
+
 /* ---- elementwise -------------------------------------------------------- */
 /* y = a + b  (tf.add, FCN.py:171), dense, n elements. */
 int seg_add(const void* a, const void* b, void* y, long n, int dtype, void* stream);

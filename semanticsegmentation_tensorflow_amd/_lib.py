@@ -22,7 +22,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libsegkern.so")
 # MFMA / no stores -- garbage results) exist only in this separate library;
 # SEG_DIAG_LIB=1 loads it instead of the product library
 DIAG_LIB_PATH = os.path.join(PKG_DIR, "build_diag", "libsegkern_diag.so")
-SOURCES = ["igemm.hip", "igemm2.hip", "igemm3.hip", "halo.hip", "halo4.hip", "dgrad_s2.hip", "wgrad.hip", "conv.hip", "eltwise.hip", "optim.hip", "smallc.hip", "augment.hip", "dense1x1.hip"]
+SOURCES = ["igemm.hip", "igemm2.hip", "igemm3.hip", "halo.hip", "halo4.hip", "dgrad_s2.hip", "wgrad.hip", "conv.hip", "eltwise.hip", "optim.hip", "smallc.hip", "augment.hip", "dense1x1.hip", "pool.hip"]
 HOST_SOURCES = ["pngdec.cpp", "crc32c.cpp"]
 HIP_HOST_SOURCES = ["timing.cpp"]   # host code against the HIP runtime API (hipcc, no kernels)
 HOST_LIBS = ["-lz"]
@@ -100,6 +100,12 @@ class SegAugView(ctypes.Structure):
     _fields_ = [("src", ctypes.c_void_p), ("H0", ctypes.c_int), ("W0", ctypes.c_int), ("x0", ctypes.c_int),
                 ("y0", ctypes.c_int), ("w", ctypes.c_int), ("h", ctypes.c_int), ("flip", ctypes.c_int),
                 ("bc", ctypes.c_int), ("bright", ctypes.c_int), ("contrast", ctypes.c_double)]
+
+
+class SegPoolDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int) for n in (
+        "N", "H", "W", "C", "kh", "kw", "sh", "sw", "pad_top", "pad_left", "OH", "OW", "ldx", "ldy", "kind",
+        "dtype")]
 
 
 class SegPrologue(ctypes.Structure):
@@ -194,6 +200,11 @@ SIGNATURES = {
     "seg_maxpool2x2_bwd_argmax": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "seg_avgpool2x2_fwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "seg_avgpool2x2_bwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "seg_pool_desc_init": (_I, [ctypes.POINTER(SegPoolDesc), _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I]),
+    "seg_pool2d_fwd": (_I, [ctypes.POINTER(SegPoolDesc), _P, _P, _P, _P]),
+    "seg_pool2d_bwd": (_I, [ctypes.POINTER(SegPoolDesc), _P, _P, _P, _P]),
+    "seg_pad2d_fwd": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "seg_pad2d_bwd": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "seg_add": (_I, [_P, _P, _P, _L, _I, _P]),
     "seg_dropout_fwd": (_I, [_P, _P, _L, _F, ctypes.c_uint64, _I, _P]),
     "seg_dropout_bwd": (_I, [_P, _P, _L, _F, ctypes.c_uint64, _I, _P]),

@@ -480,6 +480,25 @@ class BackwardMixin:
             ops.avgpool2x2_bwd(dy, dx)
             g.done(dx, acc)
 
+    def _bwd_Pool2D(self, p, n, dy, g):
+        x = n.inputs[0]
+        if id(x) in p.needs_grad:
+            dx, acc = g.dest(x)
+            ops.pool2d_bwd(n.desc, p.pool_idx.get(id(n)), dy, dx)     # a gather: dx written whole
+            g.done(dx, acc)
+
+    def _bwd_Subsample(self, p, n, dy, g):
+        # the compact gradient (the sum over the sibling convs) scattered into
+        # the full map, zeros at the pixels the stride skips
+        self._bwd_Pool2D(p, n, dy, g)
+
+    def _bwd_Pad(self, p, n, dy, g):
+        x = n.inputs[0]
+        if id(x) in p.needs_grad:
+            dx, acc = g.dest(x)
+            ops.pad2d_bwd(dy, dx, n.ops[0].attrs["pads"])
+            g.done(dx, acc)
+
     def _bwd_Add(self, p, n, dy, g):
         for t in n.inputs:
             g.contribute(t, dy)

@@ -124,6 +124,17 @@ class ForwardMixin:
     def _fwd_AvgPool(self, p, n, y, scal, seed):
         ops.avgpool2x2_fwd(p.buf[id(n.inputs[0])], y)
 
+    def _fwd_Pool2D(self, p, n, y, scal, seed):
+        # any window / stride / padding; a max pool of a train plan records its switches
+        ops.pool2d_fwd(n.desc, p.buf[id(n.inputs[0])], y, p.pool_idx.get(id(n)))
+
+    def _fwd_Subsample(self, p, n, y, scal, seed):
+        # every s-th pixel into the compact buffer a strided 1x1 conv reads (planner._lower_strided_1x1)
+        ops.pool2d_fwd(n.desc, p.buf[id(n.inputs[0])], y)
+
+    def _fwd_Pad(self, p, n, y, scal, seed):
+        ops.pad2d_fwd(p.buf[id(n.inputs[0])], y, n.ops[0].attrs["pads"])
+
     def _fwd_Add(self, p, n, y, scal, seed):
         ops.add(p.buf[id(n.inputs[0])], p.buf[id(n.inputs[1])], y)
 

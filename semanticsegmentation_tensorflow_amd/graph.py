@@ -366,6 +366,11 @@ def conv2d(input, filter, strides=(1, 1, 1, 1), padding="SAME", dilations=1, nam
     """tf.nn.conv2d; dilations an int, [dh, dw] or [1, dh, dw, 1] (per axis:
     Network/model/LidCamNet.py:45-53)."""
     sh, sw = _strides(strides)
+    if dilations is True:
+        # PSPNet50 passes True where Conv2D_Block expects the dilation
+        # (Network/model/PSPNet.py:31, :37-40: positional misbinding); TF
+        # reads the bool as the int 1
+        dilations = 1
     dh, dw = _dilations(dilations)
     if sh != sw:
         raise NotImplementedError("anisotropic stride")
@@ -425,14 +430,31 @@ def relu(features, name=None):
     return op.outputs[0]
 
 
+def pool_out(in_size, k, s, padding):
+    """TF's pooling output size along one axis (None stays None)."""
+    if in_size is None:
+        return None
+    if padding == "SAME":
+        return -(-in_size // s)
+    return (in_size - k) // s + 1
+
+
 def _pool(kind, value, ksize, strides, padding, name):
-    k = _strides(ksize)
-    s = _strides(strides)
-    if k != (2, 2) or s != (2, 2) or padding != "VALID":
-        raise NotImplementedError(f"{kind}: only 2x2 stride-2 VALID pooling is on the hot path")
-    op = Op(kind, [value], {}, name)
+    k = tuple(int(v) for v in _strides(ksize))
+    s = tuple(int(v) for v in _strides(strides))
+    if padding not in ("SAME", "VALID"):
+        raise ValueError(f"{kind}: padding {padding!r}")
     N, H, W, C = value.shape
-    op.outputs[0].shape = (N, None if H is None else H // 2, None if W is None else W // 2, C)
+    if k == (2, 2) and s == (2, 2) and padding == "VALID":
+        # the 2x2 stride-2 pools keep their own op (and the plans fused around it)
+        op = Op(kind, [value], {}, name)
+        op.outputs[0].shape = (N, None if H is None else H // 2, None if W is None else W // 2, C)
+        return op.outputs[0]
+    if min(k + s) < 1:
+        raise ValueError(f"{kind}: ksize {k} and strides {s} must be positive")
+    op = Op("Pool2D", [value], {"kind": "max" if kind == "MaxPool" else "avg", "ksize": k, "strides": s,
+                                "padding": padding}, name or kind)
+    op.outputs[0].shape = (N, pool_out(H, k[0], s[0], padding), pool_out(W, k[1], s[1], padding), C)
     return op.outputs[0]
 
 
@@ -442,6 +464,25 @@ def max_pool(value, ksize, strides, padding, name=None):
 
 def avg_pool(value, ksize, strides, padding, name=None):
     return _pool("AvgPool", value, ksize, strides, padding, name)
+
+
+def pad(tensor, paddings, mode="CONSTANT", name=None, constant_values=0):
+    """tf.pad with constant zeros on H and W (Zero_Padding, Network/utils/utils.py
+    :325-327): paddings [[0, 0], [top, bottom], [left, right], [0, 0]]."""
+    if mode != "CONSTANT" or constant_values != 0:
+        raise NotImplementedError("tf.pad: only constant zero padding")
+    rows = [tuple(int(v) for v in row) for row in paddings]
+    if len(rows) != 4 or any(len(r) != 2 for r in rows):
+        raise ValueError(f"tf.pad: paddings must be [4, 2] for an NHWC tensor, got {rows}")
+    if rows[0] != (0, 0) or rows[3] != (0, 0):
+        raise ValueError(f"tf.pad: padding on the batch or channel axis {rows}: only H and W are on the hot path")
+    (top, bottom), (left, right) = rows[1], rows[2]
+    if min(top, bottom, left, right) < 0:
+        raise ValueError(f"tf.pad: negative padding {rows}")
+    op = Op("Pad", [tensor], {"pads": (top, bottom, left, right)}, name or "Pad")
+    N, H, W, C = tensor.shape
+    op.outputs[0].shape = (N, None if H is None else H + top + bottom, None if W is None else W + left + right, C)
+    return op.outputs[0]
 
 
 def dropout(x, keep_prob, name=None):

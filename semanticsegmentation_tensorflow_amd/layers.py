@@ -159,6 +159,12 @@ def Softmax(x):
     return tf.nn.softmax(x)
 
 
+def Zero_Padding(x, paddings, name):
+    """utils.py:325-327: `paddings` zero rows / columns on every side of H and W."""
+    pad_mat = [[0, 0], [paddings, paddings], [paddings, paddings], [0, 0]]
+    return tf.pad(x, paddings=pad_mat, name=name)
+
+
 def Resize_Bilinear(x, size, name):
     return tf.image.resize_bilinear(x, size=size, align_corners=True, name=name)
 

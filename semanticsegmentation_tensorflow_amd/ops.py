@@ -14,7 +14,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import SegBnBwd, SegBnFinishSegment, SegConvDesc, SegEpilogue, SegKernelError, SegPrologue, check
+from ._lib import (SegBnBwd, SegBnFinishSegment, SegConvDesc, SegEpilogue, SegKernelError, SegPoolDesc, SegPrologue,
+                   check)
 
 F32, BF16, F16 = 0, 1, 2
 _TORCH_DT = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16}
@@ -626,6 +627,68 @@ def avgpool2x2_bwd(dy, dx, stream=None):
     check(_lib.lib().seg_avgpool2x2_bwd(ptr(dy), ptr(dx), N, H, W, C, pixel_stride(dx),
                                         pixel_stride(dy), seg_dtype(dx), stream_ptr(stream)),
           "avg_pool_grad")
+    return dx
+
+
+POOL_MAX, POOL_AVG = 0, 1
+
+
+def pool_desc(N, H, W, C, ksize, strides, padding="VALID", kind=POOL_MAX, dtype=BF16):
+    """seg_pool_desc of a [N,H,W,C] (padded C) pooling with window ksize = (kh,
+    kw), strides = (sh, sw) and TF SAME / VALID padding; ValueError where the
+    library refuses the geometry."""
+    d = SegPoolDesc()
+    (kh, kw), (sh, sw) = _hw(ksize), _hw(strides)
+    st = _lib.lib().seg_pool_desc_init(ctypes.byref(d), N, H, W, C, kh, kw, sh, sw,
+                                       SAME if padding == "SAME" else VALID, kind, dtype)
+    if st != 0:
+        raise ValueError(f"pool2d: unsupported geometry {(N, H, W, C)} window {(kh, kw)} strides {(sh, sw)} "
+                         f"{padding} ({_lib.lib().seg_status_string(st).decode()})")
+    return d
+
+
+def _pool_ld(desc, x, y):
+    d = SegPoolDesc.from_buffer_copy(desc)
+    d.ldx, d.ldy = pixel_stride(x), pixel_stride(y)
+    return d
+
+
+def pool2d_fwd(desc, x, y, idx=None, stream=None):
+    """MaxPool / AvgPool of desc: y, and (max, idx given) the switches -- one
+    byte per pooled element, row stride C, the first maximum's r * kw + s."""
+    d = _pool_ld(desc, x, y)
+    check(_lib.lib().seg_pool2d_fwd(ctypes.byref(d), ptr(x), ptr(y), ptr(idx), stream_ptr(stream)),
+          "max_pool" if desc.kind == POOL_MAX else "avg_pool")
+    return y
+
+
+def pool2d_bwd(desc, idx, dy, dx, stream=None):
+    """MaxPoolGrad (from the forward's switches) / AvgPoolGrad: dx written whole."""
+    d = _pool_ld(desc, dx, dy)
+    check(_lib.lib().seg_pool2d_bwd(ctypes.byref(d), ptr(idx), ptr(dy), ptr(dx), stream_ptr(stream)),
+          "max_pool_grad" if desc.kind == POOL_MAX else "avg_pool_grad")
+    return dx
+
+
+def pad2d_fwd(x, y, pads, stream=None):
+    """tf.pad with zeros on H and W: pads = (top, bottom, left, right)."""
+    N, H, W, C = x.shape
+    t, b, l, r = pads
+    if tuple(y.shape) != (N, H + t + b, W + l + r, C):
+        raise ValueError(f"pad: output {tuple(y.shape)} for input {tuple(x.shape)} pads {tuple(pads)}")
+    check(_lib.lib().seg_pad2d_fwd(ptr(x), pixel_stride(x), ptr(y), pixel_stride(y), N, H, W, C, t, b, l, r,
+                                   seg_dtype(x), stream_ptr(stream)), "pad")
+    return y
+
+
+def pad2d_bwd(dy, dx, pads, stream=None):
+    """Gradient of pad2d_fwd: dx = dy cropped by pads."""
+    N, H, W, C = dx.shape
+    t, b, l, r = pads
+    if tuple(dy.shape) != (N, H + t + b, W + l + r, C):
+        raise ValueError(f"pad_grad: gradient {tuple(dy.shape)} for input {tuple(dx.shape)} pads {tuple(pads)}")
+    check(_lib.lib().seg_pad2d_bwd(ptr(dy), pixel_stride(dy), ptr(dx), pixel_stride(dx), N, H, W, C, t, b, l, r,
+                                   seg_dtype(dx), stream_ptr(stream)), "pad_grad")
     return dx
 
 

@@ -11,7 +11,45 @@ from . import ops
 from .ops import round8
 
 
+class _Subsampled:
+    """Every s-th pixel of `src` as a compact tensor: made by the planner (no
+    graph op produces it), read by the strided 1x1 convs of `src`."""
+
+    def __init__(self, src, stride):
+        self.src, self.stride = src, stride
+        self.dtype = src.dtype
+
+
 class PlanMixin:
+    def _lower_strided_1x1(self, p, nodes, make_node):
+        """A 1x1 conv with stride s > 1 (the opening convs of PSPNet50's ResNet
+        stages, Network/model/PSPNet.py:57, :60, :83, :86, :121, :125) reads
+        every s-th pixel and nothing else -- out = ceil(in / s) under both
+        paddings, no pad.  It becomes a Subsample node (a 1x1-window stride-s
+        pool into a compact buffer) followed by the same conv at stride 1 on
+        that buffer: forward, filter gradient and input gradient all run the
+        stride-1 1x1 kernels, and the Subsample node's backward
+        (seg_pool2d_bwd) scatters the compact gradient into the full map,
+        zeros elsewhere.  Sibling convs subsampling one tensor at one stride
+        (conv3_1 and shortcut2) share the compact copy, and their input
+        gradients meet in its gradient buffer."""
+        out, shared = [], {}
+        for n in nodes:
+            if n.kind == "conv" and n.stride > 1 and tuple(n.w.shape[:2]) == (1, 1):
+                x, s = n.inputs[0], n.stride
+                v = shared.get((id(x), s))
+                if v is None:
+                    v = shared[(id(x), s)] = _Subsampled(x, s)
+                    N, H, W, C = p.shapes[id(x)]
+                    p.shapes[id(v)] = (N, -(-H // s), -(-W // s), C)
+                    if id(x) in p.needs_grad:
+                        p.needs_grad.add(id(v))
+                    out.append(make_node("Subsample", [], [x], v, stride=s))
+                n.inputs = [v]
+                n.stride = 1
+            out.append(n)
+        return out
+
     def _users(self, p):
         """tensor id -> the nodes reading it (as an input or as the fused skip)."""
         users = {}
@@ -114,6 +152,17 @@ class PlanMixin:
         if t in ("MaxPool", "AvgPool"):
             N, H, W, C = ins[0]
             return (N, H // 2, W // 2, C)
+        if t == "Pool2D":
+            N, H, W, C = ins[0]
+            (kh, kw), (sh, sw), pad = op.attrs["ksize"], op.attrs["strides"], op.attrs["padding"]
+            OH, OW = G.pool_out(H, kh, sh, pad), G.pool_out(W, kw, sw, pad)
+            if OH < 1 or OW < 1:
+                raise ValueError(f"{op.name}: a {kh}x{kw} window does not fit a {H}x{W} input ({pad})")
+            return (N, OH, OW, C)
+        if t == "Pad":
+            N, H, W, C = ins[0]
+            top, bottom, left, right = op.attrs["pads"]
+            return (N, H + top + bottom, W + left + right, C)
         if t == "ConcatV2":
             return tuple(ins[0][:3]) + (sum(s[3] for s in ins),)
         if t == "ResizeBilinear":
@@ -341,6 +390,20 @@ class PlanMixin:
                     ws_need = max(ws_need, ops.conv_workspace(n.desc, ops.OP_TBWD_DATA),
                                   ops.conv_workspace(n.desc, ops.OP_TBWD_FILTER),
                                   4 * 1024 * 2 * round8(Co))
+            elif n.kind in ("Pool2D", "Subsample"):
+                N, H, W, C = shp[id(n.inputs[0])]
+                if n.kind == "Subsample":
+                    # window 1x1: an average over one element is that element (no switches)
+                    k, st, pad, kind = (1, 1), (n.stride, n.stride), "VALID", ops.POOL_AVG
+                else:
+                    a = n.ops[0].attrs
+                    k, st, pad = a["ksize"], a["strides"], a["padding"]
+                    kind = ops.POOL_MAX if a["kind"] == "max" else ops.POOL_AVG
+                n.desc = ops.pool_desc(N, H, W, round8(C), k, st, pad, kind, self.cdt)
+                if kind == ops.POOL_MAX and p.train and id(n.inputs[0]) in p.needs_grad:
+                    # the forward records its switches; MaxPoolGrad reads them, not x
+                    p.pool_idx[id(n)] = torch.empty(N * n.desc.OH * n.desc.OW * round8(C), dtype=torch.uint8,
+                                                    device=dev)
             elif n.kind == "bn":
                 ws_need = max(ws_need, 4 * 1024 * 2 * round8(s[3]))
             elif n.kind == "MaxPool" and p.train and id(n.inputs[0]) in p.needs_grad:

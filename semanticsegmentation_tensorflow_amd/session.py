@@ -9,6 +9,8 @@ Compilation (per fetch set and fed shapes):
       Conv2DTranspose [+BiasAdd] [+Add]         -> tconv (bias + skip fusion)
       FusedBatchNorm [+Relu]                    -> bn
       SoftmaxXent + Mean                        -> xent (loss and dlogits)
+    and the lowering of a strided 1x1 Conv2D to a shared Subsample node + the
+    same conv at stride 1 (planner._lower_strided_1x1);
   * static device buffers (NHWC, channels padded to 8) for every activation,
     gradient and workspace -- nothing is allocated while a step runs;
   * backward in reverse order with gradients written straight into the flat
@@ -465,7 +467,7 @@ class Session(PlanMixin, ForwardMixin, BackwardMixin, StreamMixin):
                     needs_grad.add(id(op.outputs[0]))
         p.needs_grad = needs_grad
 
-        p.nodes = self._fuse_nodes(order, consumers, fetched, shp)
+        p.nodes = self._lower_strided_1x1(p, self._fuse_nodes(order, consumers, fetched, shp), _Node)
         p.fetched = fetched
         self._fold_bn_prologues(p, fetched)
         self._fold_dropout_grads(p, fetched)
@@ -545,7 +547,7 @@ class Session(PlanMixin, ForwardMixin, BackwardMixin, StreamMixin):
                                    valid_hw=op.attrs["valid_hw"]))
             elif t == "Placeholder":
                 nodes.append(_Node("input", [op], [], y))
-            elif t in ("MaxPool", "AvgPool", "Add", "Relu", "Dropout", "BiasAdd", "ConcatV2",
+            elif t in ("MaxPool", "AvgPool", "Pool2D", "Pad", "Add", "Relu", "Dropout", "BiasAdd", "ConcatV2",
                        "ResizeBilinear", "ArgMax", "ExpandDims", "Softmax", "GlobalAvgPool"):
                 nodes.append(_Node(t, [op], list(op.inputs), y))
             elif t == "Mean":

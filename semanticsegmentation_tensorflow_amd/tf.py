@@ -28,6 +28,7 @@ shape = _g.shape
 stack = _g.stack
 add = _g.add
 concat = _g.concat
+pad = _g.pad
 argmax = _g.argmax
 expand_dims = _g.expand_dims
 reduce_mean = _g.reduce_mean
