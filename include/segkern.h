@@ -430,6 +430,48 @@ int seg_pad2d_fwd(const void* x, int ldx, void* y, int ldy, int N, int H, int W,
 int seg_pad2d_bwd(const void* dy, int lddy, void* dx, int lddx, int N, int H, int W, int C,
                   int top, int bottom, int left, int right, int dtype, void* stream);
 
+/* ---- tf.nn.depthwise_conv2d, channel multiplier 1 -------------------------
+ * (SepConv_BN: Network/model/EfficientNet.py:426-462, DeepLabv3Plus.py:23-58;
+ * csrc/dwconv.hip).  One filter per channel: an HBM-bound VALU kernel, not an
+ * implicit GEMM.  w / dw are the fp32 master filter [R, S, c_valid] (TF's
+ * [R, S, C, 1]) itself, read as fp32: no packed or rounded copy.  fp32
+ * accumulation, one rounding per output, in all three dtypes. */
+typedef struct seg_dwconv_desc {
+    int N, H, W, C;            /* C padded (multiple of 8); c_valid real channels */
+    int OH, OW, R, S;
+    int stride;                /* isotropic                                      */
+    int dil_h, dil_w;
+    int pad_top, pad_left;     /* TF SAME on the effective window (k-1)*d+1: total = max((out-1)*s + k_eff - in, 0), before = total / 2 */
+    int ldx, ldy;              /* pixel strides: channel-slice views allowed     */
+    int c_valid, dtype;
+} seg_dwconv_desc;
+/* TF's shape function (padding: 0 = SAME, 1 = VALID on the effective window);
+ * C is c_valid rounded up to 8, ldx = ldy = C.  With *d untouched: SEG_EINVAL
+ * for a null pointer, a bad dtype or padding, a non-positive size, R or S > 7
+ * or an element count >= 2^31; SEG_ESHAPE for stride > 1 together with a
+ * dilation > 1 (TF's rule) or no output; SEG_EALIGN for C % 8 or c_valid > C. */
+int seg_dwconv_desc_init(seg_dwconv_desc* d, int N, int H, int W, int C, int c_valid, int R, int S,
+                         int stride, int dil_h, int dil_w, int padding, int dtype);
+/* y[n,oh,ow,c] = sum over the in-image taps of x[n, oh*s - pad_top + r*dil_h,
+ * ow*s - pad_left + q*dil_w, c] * w[r,q,c].  y is written whole: channels
+ * c_valid .. C-1 get zeros.  A descriptor seg_dwconv_desc_init would refuse
+ * (ld fields included) is refused with the same codes, writing nothing. */
+int seg_dwconv2d_fwd(const seg_dwconv_desc* d, const void* x, const float* w, void* y, void* stream);
+/* The transpose gather over dy (taps where h + pad_top - r*dil_h is a
+ * multiple of the stride and in range): dx [N,H,W,C] (ldx) is written whole,
+ * zeros where no tap reaches and in the padding channels.  No atomics, no
+ * memset. */
+int seg_dwconv2d_bwd_data(const seg_dwconv_desc* d, const void* dy, const float* w, void* dx, void* stream);
+/* dw[r,q,c] = sum over n, oh, ow of x[..] * dy[n,oh,ow,c] over the in-image
+ * terms, written whole (fp32 [R,S,c_valid]).  Two passes without float
+ * atomics -- per-workgroup partial rows in ws, then ordered column sums -- so
+ * the result is bit-identical from run to run.  ws_bytes >=
+ * seg_dwconv_bwd_filter_workspace(d) (0 for a descriptor that is refused),
+ * SEG_EWORKSPACE otherwise. */
+size_t seg_dwconv_bwd_filter_workspace(const seg_dwconv_desc* d);
+int seg_dwconv2d_bwd_filter(const seg_dwconv_desc* d, const void* x, const void* dy, float* dw, void* ws,
+                            size_t ws_bytes, void* stream);
+
 /* ---- elementwise -------------------------------------------------------- */
 /* y = a + b  (tf.add, FCN.py:171), dense, n elements. */
 int seg_add(const void* a, const void* b, void* y, long n, int dtype, void* stream);

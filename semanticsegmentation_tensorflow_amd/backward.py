@@ -458,6 +458,21 @@ class BackwardMixin:
                             g.var_dest(n.bias.var_name) if n.bias is not None else None)
         self._grad_ready([n.w.var_name] + ([n.bias.var_name] if n.bias is not None else []))
 
+    def _bwd_dwconv(self, p, n, dy, g):
+        x = n.inputs[0]
+        wn = n.w.var_name
+        if id(x) in p.needs_grad:
+            dx, acc = g.dest(x)
+            ops.dwconv2d_bwd_data(n.desc, dy, self.store.param(wn), dx)     # a gather: dx written whole
+            g.done(dx, acc)
+        if wn in p.var_set:
+            # on the side stream beside the input-gradient chain (as the conv filter gradients)
+            side = self._wgrad_side(p, n)
+            with self._beside(side):
+                ops.dwconv2d_bwd_filter(n.desc, p.buf[id(x)], dy, self.store.grad(wn),
+                                        p.wg_ws[id(n)] if side is not None else self.ws)
+        self._grad_ready([wn])
+
     def _bwd_MaxPool(self, p, n, dy, g):
         x = n.inputs[0]
         if id(n) in p.unpool_pools:

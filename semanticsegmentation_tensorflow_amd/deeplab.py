@@ -2,9 +2,9 @@
 the reference's own layer builders.
 
 The reference's DeepLabV3Plus (Network/model/DeepLabv3Plus.py:129-271) cannot
-run as written (it imports a missing utils module and its Xception /
-MobileNetV2 backbones need depthwise convolutions, which no hot-path builder
-of the reference provides), so SURVEY.md 8f-4 leaves the variant to the build.
+run as written (it imports a missing utils module, and its Xception /
+MobileNetV2 backbones are not built), so SURVEY.md 8f-4 leaves the variant to
+the build.
 This one keeps the parts of that file that ARE the DeepLab method and maps
 them onto the hot-path builders:
 
@@ -22,11 +22,16 @@ them onto the hot-path builders:
 * classifier `Last_layer` (1x1, :262) and Resize_Bilinear (align_corners,
   utils.py:329) back to the input size (:264-266).
 
-Returns (expand_dims(argmax(logits)), logits) like FCN.create().
+DeepLabSepASPP is the same backbone under the reference's EfficientSeg head
+(Network/model/EfficientNet.py:492-529): the atrous branches are SepConv_BN
+blocks (depthwise 3x3 + BN + ReLU + 1x1 + BN + ReLU, tf.nn.depthwise_conv2d)
+and a two-SepConv decoder follows at twice the feature resolution.
+
+Both return (expand_dims(argmax(logits)), logits) like FCN.create().
 """
 from . import tf
 from .layers import (STDDEV, Atrous_Conv2D_Block, Concat, Conv2D_Block, Dropout, Global_Avg_Pool, Resize_Bilinear,
-                     conv_layer, max_pool)
+                     SepConv_BN, conv_layer, max_pool)
 
 ASPP_RATES = (6, 12, 18)
 ASPP_DEPTH = 256
@@ -41,6 +46,58 @@ def atrous_conv_layer(x, num_filters, name, rate, filter_height=3, filter_width=
                             initializer=tf.random_normal_initializer(mean=0.0, stddev=STDDEV))
         b = tf.get_variable("biases", shape=[num_filters], initializer=tf.constant_initializer(0.0))
         return tf.nn.relu(tf.nn.bias_add(tf.nn.atrous_conv2d(x, W, rate, padding="SAME"), b))
+
+
+def _vgg_atrous(x):
+    h = conv_layer(x, 64, "conv1_1")
+    h = conv_layer(h, 64, "conv1_2")
+    h = max_pool(h, "pool1")
+    h = conv_layer(h, 128, "conv2_1")
+    h = conv_layer(h, 128, "conv2_2")
+    h = max_pool(h, "pool2")
+    h = conv_layer(h, 256, "conv3_1")
+    h = conv_layer(h, 256, "conv3_2")
+    h = conv_layer(h, 256, "conv3_3")
+    h = max_pool(h, "pool3")
+    h = conv_layer(h, 512, "conv4_1")
+    h = conv_layer(h, 512, "conv4_2")
+    h = conv_layer(h, 512, "conv4_3")
+    h = atrous_conv_layer(h, 512, "conv5_1", 2)
+    h = atrous_conv_layer(h, 512, "conv5_2", 2)
+    return atrous_conv_layer(h, 512, "conv5_3", 2)
+
+
+def DeepLabSepASPP(x, keep_prob, num_classes, aspp_rates=ASPP_RATES):
+    """The reference's EfficientSeg head (Network/model/EfficientNet.py:492-529:
+    separable ASPP and the two-SepConv decoder) on DeepLabASPP's VGG atrous
+    backbone.  aspp_rates= lets small inputs be tested."""
+    H, W = int(x.get_shape()[1].value), int(x.get_shape()[2].value)
+    feat = _vgg_atrous(x)
+    fh, fw = int(feat.get_shape()[1].value), int(feat.get_shape()[2].value)
+
+    b4 = Global_Avg_Pool(feat)
+    b4 = tf.expand_dims(b4, dim=1)
+    b4 = tf.expand_dims(b4, dim=1)
+    b4 = Conv2D_Block(b4, ASPP_DEPTH, filter_height=1, filter_width=1, stride=1, padding="SAME",
+                      batch_normalization=True, relu=True, name="image_pooling")
+    size_before = tf.shape(feat)
+    b4 = Resize_Bilinear(b4, size_before[1:3], name="upsampling_after_gap")
+    b0 = Conv2D_Block(feat, ASPP_DEPTH, filter_height=1, filter_width=1, stride=1, padding="SAME",
+                      batch_normalization=True, relu=True, name="aspp0")
+    branches = [b4, b0]
+    for i, r in enumerate(aspp_rates):
+        branches.append(SepConv_BN(feat, ASPP_DEPTH, f"aspp{i + 1}", rate=r, depth_activation=True))
+    cat = Concat(branches, axis=-1, name="concatenation")
+    h = Conv2D_Block(cat, ASPP_DEPTH, filter_height=1, filter_width=1, stride=1, padding="SAME",
+                     batch_normalization=True, relu=True, name="concatenation_conv")
+    h = Dropout(h, keep_prob=keep_prob)
+    h = Resize_Bilinear(h, [2 * fh, 2 * fw], name="upsampling2")      # tf.shape(feature) * 2
+    h = SepConv_BN(h, ASPP_DEPTH, "decoder_conv0", depth_activation=True)
+    h = SepConv_BN(h, ASPP_DEPTH, "decoder_conv1", depth_activation=True)
+    last = Conv2D_Block(h, num_classes, filter_height=1, filter_width=1, stride=1, padding="SAME", name="last_layer")
+    logits = Resize_Bilinear(last, [H, W], name="output")
+    pred = tf.argmax(logits, dimension=3, name="prediction")
+    return tf.expand_dims(pred, dim=3), logits
 
 
 def DeepLabASPP(x, keep_prob, num_classes):

@@ -112,6 +112,10 @@ class ForwardMixin:
         self._timed(n.desc, ops.OP_TFWD, ops.tconv2d_fwd, n.desc, x, self._pack(n, ops.PACK_TCONV_FWD), y, epi,
                     self.ws)
 
+    def _fwd_dwconv(self, p, n, y, scal, seed):
+        # tf.nn.depthwise_conv2d: reads the fp32 master filter itself
+        ops.dwconv2d_fwd(n.desc, p.buf[id(n.inputs[0])], self.store.param(n.w.var_name), y)
+
     def _fwd_MaxPool(self, p, n, y, scal, seed):
         idx = p.pool_idx.get(id(n))
         if id(n) in p.pool_fused:

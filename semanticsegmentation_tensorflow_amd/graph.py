@@ -173,6 +173,31 @@ class constant_initializer:
         self.value = value
 
 
+class glorot_uniform_initializer:
+    """TF1's default initializer of tf.get_variable (SepConv_BN's depthwise
+    filter, Network/model/EfficientNet.py:451): U(-limit, limit) with limit =
+    sqrt(6 / (fan_in + fan_out)).  TF's fans of a conv filter [..., i, o] are
+    i and o times the receptive field, so a [k, k, C, 1] depthwise filter has
+    fan_in = k k C and fan_out = k k."""
+
+    @staticmethod
+    def limit(shape):
+        shape = tuple(int(s) for s in shape)
+        if len(shape) < 1:
+            fan_in = fan_out = 1
+        elif len(shape) == 1:
+            fan_in = fan_out = shape[0]
+        else:
+            field = 1
+            for s in shape[:-2]:
+                field *= s
+            fan_in, fan_out = shape[-2] * field, shape[-1] * field
+        return (6.0 / (fan_in + fan_out)) ** 0.5
+
+    def __repr__(self):
+        return "glorot_uniform"
+
+
 ones_initializer = lambda: constant_initializer(1.0)  # noqa: E731
 zeros_initializer = lambda: constant_initializer(0.0)  # noqa: E731
 
@@ -388,6 +413,33 @@ def conv2d(input, filter, strides=(1, 1, 1, 1), padding="SAME", dilations=1, nam
 
 def atrous_conv2d(value, filters, rate, padding="SAME", name=None):
     return conv2d(value, filters, 1, padding, rate, name)
+
+
+def depthwise_conv2d(input, filter, strides, padding, rate=None, name=None):
+    """tf.nn.depthwise_conv2d with channel multiplier 1 (SepConv_BN,
+    Network/model/EfficientNet.py:453: strides=[1, s, s, 1], rate=[r, r]);
+    strides an int or a 4-list, rate None, an int or [rh, rw]."""
+    sh, sw = (int(v) for v in _strides(strides))
+    if sh != sw:
+        raise NotImplementedError("anisotropic stride")
+    rh, rw = (1, 1) if rate is None else ((int(rate),) * 2 if isinstance(rate, int) else
+                                          tuple(int(v) for v in rate))
+    if padding not in ("SAME", "VALID"):
+        raise ValueError(f"depthwise_conv2d: padding {padding!r}")
+    if min(sh, rh, rw) < 1:
+        raise ValueError(f"depthwise_conv2d: strides {strides} and rate {rate} must be positive")
+    if sh > 1 and (rh > 1 or rw > 1):          # TF: "rate > 1 requires strides == 1"
+        raise ValueError(f"depthwise_conv2d: rate {(rh, rw)} with stride {sh}: one of them must be 1")
+    R, S, C, M = filter.shape
+    if M != 1:
+        raise NotImplementedError(f"depthwise_conv2d: channel multiplier {M} (only 1 is on the hot path)")
+    N, H, W, Ci = input.shape
+    if Ci is not None and Ci != C:
+        raise ValueError(f"depthwise_conv2d: input depth {Ci} != filter depth {C}")
+    op = Op("DepthwiseConv2D", [input, filter], {"stride": sh, "rate": (rh, rw), "padding": padding},
+            name or "depthwise")
+    op.outputs[0].shape = (N, _pads(H, R, sh, rh, padding), _pads(W, S, sw, rw, padding), C)
+    return op.outputs[0]
 
 
 def conv2d_transpose(value, filter, output_shape, strides, padding="SAME", name=None):

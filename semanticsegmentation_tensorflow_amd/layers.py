@@ -165,6 +165,34 @@ def Zero_Padding(x, paddings, name):
     return tf.pad(x, paddings=pad_mat, name=name)
 
 
+def SepConv_BN(x, filters, prefix, stride=1, kernel_size=3, rate=1, depth_activation=False):
+    """Depthwise k x k -> BN -> 1x1 conv + BN + ReLU (Network/model/EfficientNet.py
+    :426-462, DeepLabv3Plus.py:23-58).  stride 1: SAME; otherwise explicit zero
+    padding of the effective kernel (pad_beg, pad_end) and VALID, the "right SAME
+    padding for even kernel sizes" of DeepLabv3Plus.py:37-43.  depth_activation:
+    ReLU after the depthwise BN instead of before the depthwise conv."""
+    if stride == 1:
+        depth_padding = "SAME"
+    else:
+        k_eff = kernel_size + (kernel_size - 1) * (rate - 1)
+        pad_beg = (k_eff - 1) // 2
+        pad_end = k_eff - 1 - pad_beg
+        x = tf.pad(x, paddings=[[0, 0], [pad_beg, pad_end], [pad_beg, pad_end], [0, 0]],
+                   name=prefix + "zero_paddings")
+        depth_padding = "VALID"
+    if not depth_activation:
+        x = ReLU(x)
+    filter_shape = [kernel_size, kernel_size, int(x.get_shape()[-1].value), 1]
+    filter = tf.get_variable(prefix + "_filter", shape=filter_shape, initializer=tf.glorot_uniform_initializer())
+    x = tf.nn.depthwise_conv2d(x, filter=filter, strides=[1, stride, stride, 1], rate=[rate, rate],
+                               padding=depth_padding, name=prefix + "_depthwise")
+    x = Batch_Normalization(x)
+    if depth_activation:
+        x = ReLU(x)
+    return Conv2D_Block(x, filters, filter_height=1, filter_width=1, stride=1, padding="SAME",
+                        batch_normalization=True, relu=True, name=prefix + "_pointwise_BN")
+
+
 def Resize_Bilinear(x, size, name):
     return tf.image.resize_bilinear(x, size=size, align_corners=True, name=name)
 

@@ -14,8 +14,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (SegBnBwd, SegBnFinishSegment, SegConvDesc, SegEpilogue, SegKernelError, SegPoolDesc, SegPrologue,
-                   check)
+from ._lib import (SegBnBwd, SegBnFinishSegment, SegConvDesc, SegDwconvDesc, SegEpilogue, SegKernelError, SegPoolDesc,
+                   SegPrologue, check)
 
 F32, BF16, F16 = 0, 1, 2
 _TORCH_DT = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16}
@@ -690,6 +690,60 @@ def pad2d_bwd(dy, dx, pads, stream=None):
     check(_lib.lib().seg_pad2d_bwd(ptr(dy), pixel_stride(dy), ptr(dx), pixel_stride(dx), N, H, W, C, t, b, l, r,
                                    seg_dtype(dx), stream_ptr(stream)), "pad_grad")
     return dx
+
+
+def dwconv_desc(N, H, W, C, c_valid, R, S, stride=1, rate=1, padding="SAME", dtype=BF16):
+    """seg_dwconv_desc of tf.nn.depthwise_conv2d (channel multiplier 1) on a
+    [N,H,W,C] input (C padded, c_valid real channels) with an [R,S,c_valid]
+    filter; rate an int or (rh, rw).  ValueError where the library refuses."""
+    d = SegDwconvDesc()
+    dh, dw = _hw(rate)
+    st = _lib.lib().seg_dwconv_desc_init(ctypes.byref(d), N, H, W, C, c_valid, R, S, int(stride), dh, dw,
+                                         SAME if padding == "SAME" else VALID, dtype)
+    if st != 0:
+        raise ValueError(f"depthwise_conv2d: unsupported geometry {(N, H, W, C)} filter {(R, S)} stride {stride} "
+                         f"rate {(dh, dw)} {padding} ({_lib.lib().seg_status_string(st).decode()})")
+    return d
+
+
+def _dwconv_ld(desc, x, y):
+    d = SegDwconvDesc.from_buffer_copy(desc)
+    d.ldx, d.ldy = pixel_stride(x), pixel_stride(y)
+    return d
+
+
+def dwconv2d_fwd(desc, x, w, y, stream=None):
+    """y = depthwise_conv2d(x, w): w the fp32 master filter [R,S,c_valid(,1)]."""
+    d = _dwconv_ld(desc, x, y)
+    check(_lib.lib().seg_dwconv2d_fwd(ctypes.byref(d), ptr(x), ptr(w), ptr(y), stream_ptr(stream)),
+          "depthwise_conv2d")
+    return y
+
+
+def dwconv2d_bwd_data(desc, dy, w, dx, stream=None):
+    """DepthwiseConv2dNativeBackpropInput as a gather: dx written whole."""
+    d = _dwconv_ld(desc, dx, dy)
+    check(_lib.lib().seg_dwconv2d_bwd_data(ctypes.byref(d), ptr(dy), ptr(w), ptr(dx), stream_ptr(stream)),
+          "depthwise_conv2d_grad_input")
+    return dx
+
+
+def dwconv_bwd_filter_workspace(desc):
+    return int(_lib.lib().seg_dwconv_bwd_filter_workspace(ctypes.byref(desc)))
+
+
+def dwconv2d_bwd_filter(desc, x, dy, dw, ws=None, stream=None):
+    """DepthwiseConv2dNativeBackpropFilter: dw fp32 [R,S,c_valid(,1)], written
+    whole; ws a Workspace or a uint8 tensor of dwconv_bwd_filter_workspace bytes."""
+    d = _dwconv_ld(desc, x, dy)
+    need = dwconv_bwd_filter_workspace(d)
+    if isinstance(ws, torch.Tensor):
+        wsp, wss = ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel())
+    else:
+        wsp, wss = (ws or Workspace(x.device)).ptr_size(need)
+    check(_lib.lib().seg_dwconv2d_bwd_filter(ctypes.byref(d), ptr(x), ptr(dy), ptr(dw), wsp, wss,
+                                             stream_ptr(stream)), "depthwise_conv2d_grad_filter")
+    return dw
 
 
 def add(a, b, y, stream=None):

@@ -143,6 +143,14 @@ class PlanMixin:
             ops.tconv_desc(N, H, W, C, os_[1], os_[2], Co, R, S, op.attrs["stride"],
                            op.attrs["padding"], self.cdt)  # raises on TF shape-rule violation
             return (N, os_[1], os_[2], Co)
+        if t == "DepthwiseConv2D":
+            N, H, W, C = ins[0]
+            R, S, Ci, _ = ins[1]
+            if Ci != C:
+                raise ValueError(f"{op.name}: input depth {C} != filter depth {Ci}")
+            d = ops.dwconv_desc(N, H, W, round8(C), C, R, S, op.attrs["stride"], op.attrs["rate"],
+                                op.attrs["padding"], self.cdt)
+            return (N, d.OH, d.OW, C)
         if t in ("BiasAdd", "Relu", "Dropout", "FusedBatchNorm", "Softmax"):
             return ins[0]
         if t == "Add":
@@ -404,6 +412,14 @@ class PlanMixin:
                     # the forward records its switches; MaxPoolGrad reads them, not x
                     p.pool_idx[id(n)] = torch.empty(N * n.desc.OH * n.desc.OW * round8(C), dtype=torch.uint8,
                                                     device=dev)
+            elif n.kind == "dwconv":
+                # tf.nn.depthwise_conv2d: a node kind of its own, outside every
+                # conv fusion (its filter is the fp32 master, no packed copy)
+                N, H, W, C = shp[id(n.inputs[0])]
+                R, S, _, _ = n.w.shape
+                n.desc = ops.dwconv_desc(N, H, W, round8(C), C, R, S, n.stride, n.rate, n.padding, self.cdt)
+                if p.train:
+                    ws_need = max(ws_need, ops.dwconv_bwd_filter_workspace(n.desc))
             elif n.kind == "bn":
                 ws_need = max(ws_need, 4 * 1024 * 2 * round8(s[3]))
             elif n.kind == "MaxPool" and p.train and id(n.inputs[0]) in p.needs_grad:
@@ -552,6 +568,8 @@ class PlanMixin:
                 covered.add(n.w.var_name)
                 if n.bias is not None:
                     covered.add(n.bias.var_name)
+            elif n.kind == "dwconv":
+                covered.add(n.w.var_name)
             elif n.kind == "bn":
                 covered.update([n.gamma.var_name, n.beta.var_name])
             elif n.kind == "BiasAdd":
@@ -585,6 +603,10 @@ class PlanMixin:
             if n.kind in ("conv", "tconv"):
                 op = ops.OP_BWD_FILTER if n.kind == "conv" else ops.OP_TBWD_FILTER
                 p.wg_ws[id(n)] = torch.empty(max(256, ops.conv_workspace(n.desc, op)),
+                                             dtype=torch.uint8, device=self.device)
+            elif n.kind == "dwconv":
+                # its own partial rows: the filter gradient runs on the side stream
+                p.wg_ws[id(n)] = torch.empty(max(256, ops.dwconv_bwd_filter_workspace(n.desc)),
                                              dtype=torch.uint8, device=self.device)
         p.var_names = [v.var_name for v in p.train.attrs["var_list"]]
         p.var_set = set(p.var_names)

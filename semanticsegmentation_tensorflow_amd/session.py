@@ -531,6 +531,11 @@ class Session(PlanMixin, ForwardMixin, BackwardMixin, StreamMixin):
                                    bias=b.inputs[1] if b is not None else None, residual=res,
                                    stride=op.attrs["stride"], padding=op.attrs["padding"],
                                    output_shape=op.attrs["output_shape"]))
+            elif t == "DepthwiseConv2D":
+                # a kind of its own: the BN / ReLU around it stay standalone nodes
+                x, w = op.inputs
+                nodes.append(_Node("dwconv", [op], [x], y, w=w, stride=op.attrs["stride"], rate=op.attrs["rate"],
+                                   padding=op.attrs["padding"]))
             elif t == "FusedBatchNorm":
                 x, gamma, beta = op.inputs
                 chain = [op]

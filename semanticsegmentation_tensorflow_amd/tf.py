@@ -19,6 +19,7 @@ variable_scope = _g.variable_scope
 name_scope = _g.name_scope
 random_normal_initializer = _g.random_normal_initializer
 constant_initializer = _g.constant_initializer
+glorot_uniform_initializer = _g.glorot_uniform_initializer
 trainable_variables = _g.trainable_variables
 global_variables = _g.global_variables
 global_variables_initializer = _g.global_variables_initializer
@@ -40,6 +41,7 @@ scalar_mul = _g.scalar_mul
 nn = SimpleNamespace(
     conv2d=_g.conv2d,
     atrous_conv2d=_g.atrous_conv2d,
+    depthwise_conv2d=_g.depthwise_conv2d,
     conv2d_transpose=_g.conv2d_transpose,
     bias_add=_g.bias_add,
     relu=_g.relu,

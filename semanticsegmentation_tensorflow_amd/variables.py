@@ -34,6 +34,11 @@ def init_value(var: G.Variable, seed: int = 0) -> np.ndarray:
         rng = np.random.Generator(np.random.Philox(key=[seed & 0xFFFFFFFFFFFFFFFF, key]))
         return (rng.standard_normal(shape, dtype=np.float32) * np.float32(ini.stddev)
                 + np.float32(ini.mean)).astype(np.float32)
+    if isinstance(ini, G.glorot_uniform_initializer):
+        key = zlib.crc32(var.var_name.encode()) & 0xFFFFFFFF
+        rng = np.random.Generator(np.random.Philox(key=[seed & 0xFFFFFFFFFFFFFFFF, key]))
+        lim = np.float32(ini.limit(shape))
+        return ((rng.random(shape, dtype=np.float32) * np.float32(2.0) - np.float32(1.0)) * lim).astype(np.float32)
     if callable(ini):
         return np.asarray(ini(shape), dtype=np.float32)
     raise TypeError(f"unsupported initializer {ini!r}")
