@@ -472,6 +472,55 @@ size_t seg_dwconv_bwd_filter_workspace(const seg_dwconv_desc* d);
 int seg_dwconv2d_bwd_filter(const seg_dwconv_desc* d, const void* x, const void* dy, float* dw, void* ws,
                             size_t ws_bytes, void* stream);
 
+/* ---- MBConvBlock: swish / sigmoid and squeeze-excite ------------------------
+ * (Network/model/EfficientNet.py:153-210: tf.nn.swish after expand_bn and bn
+ * :162-166, :175-179; Global_Avg_Pool :184; the se_reduce / se_expand
+ * activations :190-193; tf.math.multiply :194; csrc/mbconv.hip).  NHWC with
+ * pixel strides ld*, C % 8 == 0, f32 / bf16 / f16, fp32 arithmetic rounded
+ * once.  Channels c_valid .. C-1 of every output are written as exact zeros
+ * (sigmoid(0) is 0.5: the padding is not left to the arithmetic).  Every
+ * reduction is two passes -- per-workgroup fp32 partial rows, summed in row
+ * order -- without float atomics: bit-identical from run to run.  Anything
+ * not covered is refused with nothing written: SEG_EINVAL for a null or
+ * misaligned (16-byte) pointer, a bad dtype / act / flags, a non-positive
+ * size, ld < C, gamma without beta, or P * ld >= 2^31 elements; SEG_EALIGN for
+ * C % 8, c_valid > C or an ld that is not a whole number of 16-byte chunks;
+ * SEG_EWORKSPACE for a workspace smaller than the query says. */
+enum seg_act { SEG_ACT_SWISH = 1, SEG_ACT_SIGMOID = 2 };
+/* y = act(x * gamma / sqrt(1 + eps) + beta), the frozen-stat BatchNorm of
+ * seg_bn_relu_fwd followed by swish (z * sigmoid(z)) or sigmoid.  gamma ==
+ * beta == NULL: the plain activation (Conv2D_Block(..., activation=...) on the
+ * squeeze-excite vectors).  Finite for any finite z: exp overflowing to inf
+ * gives sigmoid 0 or 1. */
+int seg_bn_act_fwd(const void* x, int ldx, void* y, int ldy, const float* gamma, const float* beta,
+                   float eps, long P, int C, int c_valid, int act, int dtype, void* stream);
+/* z and sigmoid(z) recomputed from x (the forward output is not read).
+ * swish: dz = dy * s * (1 + z * (1 - s)); sigmoid: dz = dy * s * (1 - s).
+ * dx = dz * gamma / sqrt(1 + eps) (flags bit 1: dx += ..., as seg_bn_relu_bwd);
+ * dgamma = sum(dz * x) / sqrt(1 + eps), dbeta = sum(dz), fp32 [c_valid].
+ * gamma == beta == NULL: dx = dz, dgamma and dbeta must be NULL, no workspace. */
+size_t seg_bn_act_bwd_workspace(long P, int C);
+int seg_bn_act_bwd(const void* x, int ldx, const void* dy, int lddy, void* dx, int lddx,
+                   const float* gamma, const float* beta, float eps, float* dgamma, float* dbeta, long P,
+                   int C, int c_valid, int act, int flags, int dtype, void* ws, size_t ws_bytes,
+                   void* stream);
+/* y[n, c] = scale * sum_hw x[n, h, w, c], y dense [N, C] in the compute dtype:
+ * seg_spatial_reduce for any C (a loop over chunk groups) and without
+ * atomics. */
+size_t seg_se_squeeze_workspace(int N, int H, int W, int C);
+int seg_se_squeeze(const void* x, int ldx, void* y, int N, int H, int W, int C, int c_valid, float scale,
+                   void* ws, size_t ws_bytes, int dtype, void* stream);
+/* y[n, h, w, c] = x[n, h, w, c] * s[n, c], s dense [N, C] in the compute dtype. */
+int seg_se_excite_fwd(const void* x, int ldx, const void* s, void* y, int ldy, int N, int H, int W, int C,
+                      int c_valid, int dtype, void* stream);
+/* dx = dy * s (flags bit 1: dx += ...) and ds[n, c] = sum_hw dy * x (dense
+ * [N, C], compute dtype, rounded once) in one pass over x and dy; the partial
+ * sums are per (image, pixel slice): a workgroup never spans two images. */
+size_t seg_se_excite_bwd_workspace(int N, int H, int W, int C);
+int seg_se_excite_bwd(const void* x, int ldx, const void* s, const void* dy, int lddy, void* dx, int lddx,
+                      void* ds, int N, int H, int W, int C, int c_valid, int flags, void* ws,
+                      size_t ws_bytes, int dtype, void* stream);
+
 /* ---- elementwise -------------------------------------------------------- */
 /* y = a + b  (tf.add, FCN.py:171), dense, n elements. */
 int seg_add(const void* a, const void* b, void* y, long n, int dtype, void* stream);

@@ -540,6 +540,13 @@ class BackwardMixin:
         x = n.inputs[0]
         store = self.store
         dx, acc, accf = g.kernel_dest(x)
+        if n.act is not None:               # BatchNorm + swish: z and sigmoid(z) recomputed from x
+            ops.bn_act_bwd(p.buf[id(x)], dy, dx, store.param(n.gamma.var_name), store.param(n.beta.var_name),
+                           g.var_dest(n.gamma.var_name), g.var_dest(n.beta.var_name), p.shapes[id(x)][3], n.act,
+                           n.eps, self.ws, accumulate=accf)
+            g.done(dx, acc)
+            self._grad_ready([n.gamma.var_name, n.beta.var_name])
+            return
         drop = None
         c = p.drop_fold.get(id(n))
         if c is not None and _drops(c):
@@ -551,6 +558,33 @@ class BackwardMixin:
                         n.eps, self.ws, accumulate=accf, beta=store.param(n.beta.var_name), dropout=drop)
         g.done(dx, acc)
         self._grad_ready([n.gamma.var_name, n.beta.var_name])
+
+    def _bwd_act(self, p, n, dy, g):
+        x = n.inputs[0]
+        if id(x) in p.needs_grad:
+            dx, acc = g.dest(x)
+            ops.bn_act_bwd(p.buf[id(x)], dy, dx, None, None, None, None, p.shapes[id(x)][3], n.act)
+            g.done(dx, acc)
+
+    def _bwd_se_excite(self, p, n, dy, g):
+        # dx = dy * s and ds = sum_hw dy * x in one pass; x's other reader (the
+        # squeeze) adds its share through dest / done like any second reader
+        x, s = n.inputs
+        xb = p.buf[id(x)]
+        cv = p.shapes[id(x)][3]
+        if id(x) in p.needs_grad:
+            dx, acc = g.dest(x)
+        else:
+            dx, acc = p.scratch(("sx", id(x)), torch.zeros_like, xb), None
+        if id(s) in p.needs_grad:
+            ds, sacc = g.dest(s)
+        else:
+            ds, sacc = p.scratch(("ss", id(s)), torch.zeros_like, p.buf[id(s)]), None
+        ops.se_excite_bwd(xb, p.buf[id(s)], dy, dx, ds, cv, self.ws)
+        if id(x) in p.needs_grad:
+            g.done(dx, acc)
+        if id(s) in p.needs_grad:
+            g.done(ds, sacc)
 
     def _bwd_Relu(self, p, n, dy, g):
         x = n.inputs[0]

@@ -72,10 +72,21 @@ def DeepLabSepASPP(x, keep_prob, num_classes, aspp_rates=ASPP_RATES):
     separable ASPP and the two-SepConv decoder) on DeepLabASPP's VGG atrous
     backbone.  aspp_rates= lets small inputs be tested."""
     H, W = int(x.get_shape()[1].value), int(x.get_shape()[2].value)
-    feat = _vgg_atrous(x)
+    logits = sep_aspp_head(_vgg_atrous(x), keep_prob, num_classes, (H, W), aspp_rates=aspp_rates)
+    pred = tf.argmax(logits, dimension=3, name="prediction")
+    return tf.expand_dims(pred, dim=3), logits
+
+
+def sep_aspp_head(feat, keep_prob, num_classes, out_hw, aspp_rates=ASPP_RATES, pool_name="global_avg_pooling"):
+    """The reference's EfficientSeg decoder (Network/model/EfficientNet.py:492-529)
+    on feature map `feat`: image pooling, a 1x1 branch and three SepConv_BN
+    atrous branches, concatenated and projected, Dropout, x2 upsampling, two
+    SepConv_BN blocks, the 1x1 classifier and the resize to out_hw.  Shared by
+    DeepLabSepASPP and efficientnet.EfficientSeg; returns the logits."""
+    H, W = out_hw
     fh, fw = int(feat.get_shape()[1].value), int(feat.get_shape()[2].value)
 
-    b4 = Global_Avg_Pool(feat)
+    b4 = Global_Avg_Pool(feat, name=pool_name)
     b4 = tf.expand_dims(b4, dim=1)
     b4 = tf.expand_dims(b4, dim=1)
     b4 = Conv2D_Block(b4, ASPP_DEPTH, filter_height=1, filter_width=1, stride=1, padding="SAME",
@@ -95,9 +106,7 @@ def DeepLabSepASPP(x, keep_prob, num_classes, aspp_rates=ASPP_RATES):
     h = SepConv_BN(h, ASPP_DEPTH, "decoder_conv0", depth_activation=True)
     h = SepConv_BN(h, ASPP_DEPTH, "decoder_conv1", depth_activation=True)
     last = Conv2D_Block(h, num_classes, filter_height=1, filter_width=1, stride=1, padding="SAME", name="last_layer")
-    logits = Resize_Bilinear(last, [H, W], name="output")
-    pred = tf.argmax(logits, dimension=3, name="prediction")
-    return tf.expand_dims(pred, dim=3), logits
+    return Resize_Bilinear(last, [H, W], name="output")
 
 
 def DeepLabASPP(x, keep_prob, num_classes):

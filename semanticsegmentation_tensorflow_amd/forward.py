@@ -146,8 +146,20 @@ class ForwardMixin:
         if id(n) in p.folded or id(n) in p.bn_out2_done:
             return                          # applied by its conv's operand prologue / written by its conv
         C = p.shapes[id(n.inputs[0])][3]
+        if n.act is not None:               # BatchNorm + swish (MBConvBlock)
+            ops.bn_act_fwd(p.buf[id(n.inputs[0])], y, self.store.param(n.gamma.var_name),
+                           self.store.param(n.beta.var_name), C, n.act, n.eps)
+            return
         ops.bn_relu_fwd(p.buf[id(n.inputs[0])], y, self.store.param(n.gamma.var_name),
                         self.store.param(n.beta.var_name), C, n.relu, n.eps)
+
+    def _fwd_act(self, p, n, y, scal, seed):
+        # a standalone swish / sigmoid (the squeeze-excite vectors): no affine
+        ops.bn_act_fwd(p.buf[id(n.inputs[0])], y, None, None, p.shapes[id(n.inputs[0])][3], n.act)
+
+    def _fwd_se_excite(self, p, n, y, scal, seed):
+        x, s = n.inputs
+        ops.se_excite_fwd(p.buf[id(x)], p.buf[id(s)], y, p.shapes[id(x)][3])
 
     def _fwd_Relu(self, p, n, y, scal, seed):
         self._relu_fwd(p.buf[id(n.inputs[0])], y)
@@ -189,6 +201,10 @@ class ForwardMixin:
 
     def _fwd_GlobalAvgPool(self, p, n, y, scal, seed):
         x = p.buf[id(n.inputs[0])]
+        if not ops.spatial_reduce_fits(x.shape[3], self.cdt):
+            # wider than seg_spatial_reduce takes (EfficientNet's 1152-channel fp32 maps): the squeeze kernel
+            ops.se_squeeze(x, y, p.shapes[id(n.inputs[0])][3], 1.0 / (x.shape[1] * x.shape[2]), self.ws)
+            return
         ops.spatial_reduce(x, y, 1.0 / (x.shape[1] * x.shape[2]), self.ws)
 
     def _fwd_ExpandDims(self, p, n, y, scal, seed):

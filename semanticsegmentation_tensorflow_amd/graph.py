@@ -482,6 +482,43 @@ def relu(features, name=None):
     return op.outputs[0]
 
 
+def swish(features, name=None):
+    """tf.nn.swish: x * sigmoid(x) (MBConvBlock, Network/model/EfficientNet.py:166, :179)."""
+    op = Op("Swish", [features], {}, name)
+    op.outputs[0].shape = features.shape
+    return op.outputs[0]
+
+
+def sigmoid(x, name=None):
+    """tf.nn.sigmoid / tf.sigmoid (the se_expand gate, EfficientNet.py:192-193)."""
+    op = Op("Sigmoid", [x], {}, name)
+    op.outputs[0].shape = x.shape
+    return op.outputs[0]
+
+
+def multiply(x, y, name=None):
+    """tf.math.multiply of a feature map [N,H,W,C] with a per-image channel
+    gate [N,1,1,C], in either order (se_excite, EfficientNet.py:194); no other
+    broadcast is on the hot path."""
+    def gate(t):
+        return t.shape is not None and len(t.shape) == 4 and t.shape[1] == 1 and t.shape[2] == 1
+
+    def fmap(t):
+        return t.shape is not None and len(t.shape) == 4
+
+    if fmap(x) and gate(y):
+        a, s = x, y
+    elif fmap(y) and gate(x):
+        a, s = y, x
+    else:
+        raise NotImplementedError(f"multiply: only [N,H,W,C] x [N,1,1,C], got {x.shape} and {y.shape}")
+    if a.shape[3] != s.shape[3] or (a.shape[0] is not None and s.shape[0] is not None and a.shape[0] != s.shape[0]):
+        raise NotImplementedError(f"multiply: only [N,H,W,C] x [N,1,1,C], got {x.shape} and {y.shape}")
+    op = Op("Mul", [a, s], {}, name)
+    op.outputs[0].shape = a.shape
+    return op.outputs[0]
+
+
 def pool_out(in_size, k, s, padding):
     """TF's pooling output size along one axis (None stays None)."""
     if in_size is None:
@@ -563,8 +600,11 @@ def batch_normalization(inputs, epsilon=1e-3, name=None):
     """tf.layers.batch_normalization(x) with training=False (utils.py:300-301):
     frozen moving stats (0, 1) -> y = gamma*x/sqrt(1+eps) + beta."""
     g = get_default_graph()
-    base = name or ("batch_normalization" if g.bn_count == 0 else f"batch_normalization_{g.bn_count}")
-    g.bn_count += 1
+    if name:                   # TF1: a given name does not consume a default-name index
+        base = name
+    else:
+        base = "batch_normalization" if g.bn_count == 0 else f"batch_normalization_{g.bn_count}"
+        g.bn_count += 1
     C = inputs.shape[3]
     with _root_scope():
         gamma = get_variable(f"{base}/gamma", [C], constant_initializer(1.0))

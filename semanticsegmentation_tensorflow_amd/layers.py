@@ -70,14 +70,28 @@ def Conv2D_Layer(x, num_filters, filter_height=3, filter_width=3, stride=1, padd
 
 
 def Conv2D_Block(x, num_filters, filter_height=3, filter_width=3, stride=1, padding="SAME", dilation=1,
-                 batch_normalization=False, relu=False, name=None):
-    """utils.py:186-208 -- defaults: no BN, no ReLU."""
+                 batch_normalization=False, relu=False, name=None, activation=None):
+    """utils.py:186-208 -- defaults: no BN, no ReLU.
+
+    activation: None, 'relu', 'swish' or 'sigmoid', applied after the optional
+    BatchNorm -- the keyword Network/model/EfficientNet.py passes (:190-193,
+    :460, :496).  The module that defines it there (Utils_EfficientNet) is
+    absent from the reference, so these are the semantics: the activation its
+    name says, in the place `relu=True` has."""
+    if activation not in (None, "relu", "swish", "sigmoid"):
+        raise ValueError(f"Conv2D_Block: activation {activation!r}")
     conv = Conv2D_Layer(x, num_filters, filter_height=filter_height, filter_width=filter_width, stride=stride,
                         padding=padding, dilation=dilation, name=name)
     if batch_normalization is True:
         conv = Batch_Normalization(conv)
     if relu is True:
         conv = tf.nn.relu(conv)
+    if activation == "relu":
+        conv = tf.nn.relu(conv)
+    elif activation == "swish":
+        conv = tf.nn.swish(conv)
+    elif activation == "sigmoid":
+        conv = tf.nn.sigmoid(conv)
     return conv
 
 
@@ -127,9 +141,16 @@ def Deconv2D_Block(x, shape, num_filters, output_shape, filter_height=4, filter_
     return deconv
 
 
-def Batch_Normalization(x):
-    """tf.layers.batch_normalization(x): training=False, frozen stats (utils.py:300-301)."""
-    return tf.layers.batch_normalization(x)
+def Batch_Normalization(x, axis=3, name=None):
+    """tf.layers.batch_normalization(x): training=False, frozen stats (utils.py:300-301).
+
+    axis / name: the arguments Network/model/EfficientNet.py passes (:162, :175,
+    :201); its Utils_EfficientNet module is absent from the reference, so these
+    are the semantics: the channel axis of NHWC (the only one on the hot path)
+    and the layer's variable scope, as tf.layers.batch_normalization(name=)."""
+    if axis not in (3, -1):
+        raise NotImplementedError("Batch_Normalization: only the channel axis of NHWC")
+    return tf.layers.batch_normalization(x, name=name)
 
 
 def ReLU(x):
@@ -146,9 +167,9 @@ def Avg_Pooling(x, name, filter_height=2, filter_width=2, stride_height=2, strid
                           strides=[1, stride_height, stride_width, 1], padding=padding, name=name)
 
 
-def Global_Avg_Pool(x, stride=1):
-    """utils.py:312-313: tflearn global_avg_pool -> [N, C]."""
-    return tf.nn.global_avg_pool(x, name="global_avg_pooling")
+def Global_Avg_Pool(x, stride=1, name="global_avg_pooling"):
+    """utils.py:312-313: tflearn global_avg_pool -> [N, C] (name=: EfficientNet.py:184, :493)."""
+    return tf.nn.global_avg_pool(x, name=name)
 
 
 def Dropout(x, keep_prob):

@@ -746,6 +746,89 @@ def dwconv2d_bwd_filter(desc, x, dy, dw, ws=None, stream=None):
     return dw
 
 
+ACT_SWISH, ACT_SIGMOID = 1, 2
+_ACTS = {"swish": ACT_SWISH, "sigmoid": ACT_SIGMOID}
+
+
+def _ws_arg(ws, need, device):
+    """(pointer, size) of a Workspace or of a uint8 tensor given as workspace."""
+    if isinstance(ws, torch.Tensor):
+        return ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel())
+    return (ws or Workspace(device)).ptr_size(need)
+
+
+def bn_act_fwd(x, y, gamma, beta, c_valid, act, eps=1e-3, stream=None):
+    """y = act(x * gamma / sqrt(1 + eps) + beta), act "swish" or "sigmoid"
+    (MBConvBlock, Network/model/EfficientNet.py:162-179); gamma = beta = None:
+    the plain activation.  Padding channels of y are written as zeros."""
+    C = x.shape[-1]
+    check(_lib.lib().seg_bn_act_fwd(ptr(x), pixel_stride(x), ptr(y), pixel_stride(y), ptr(gamma), ptr(beta),
+                                    float(eps), x.numel() // C, C, int(c_valid), _ACTS[act], seg_dtype(x),
+                                    stream_ptr(stream)), act)
+    return y
+
+
+def bn_act_bwd_workspace(P, C):
+    return int(_lib.lib().seg_bn_act_bwd_workspace(int(P), int(C)))
+
+
+def bn_act_bwd(x, dy, dx, gamma, beta, dgamma, dbeta, c_valid, act, eps=1e-3, ws=None, stream=None,
+               accumulate=False):
+    """Gradient of bn_act_fwd from x (z and sigmoid(z) recomputed); with gamma =
+    beta = None there is no dgamma / dbeta and no workspace."""
+    C = x.shape[-1]
+    P = x.numel() // C
+    if gamma is None:
+        wsp, wss = None, ctypes.c_size_t(0)
+    else:
+        wsp, wss = _ws_arg(ws, bn_act_bwd_workspace(P, C), x.device)
+    check(_lib.lib().seg_bn_act_bwd(ptr(x), pixel_stride(x), ptr(dy), pixel_stride(dy), ptr(dx), pixel_stride(dx),
+                                    ptr(gamma), ptr(beta), float(eps), ptr(dgamma), ptr(dbeta), P, C, int(c_valid),
+                                    _ACTS[act], 2 if accumulate else 0, seg_dtype(x), wsp, wss, stream_ptr(stream)),
+          act + "_grad")
+    return dx
+
+
+def se_squeeze_workspace(N, H, W, C):
+    return int(_lib.lib().seg_se_squeeze_workspace(N, H, W, C))
+
+
+def se_squeeze(x, y, c_valid, scale, ws=None, stream=None):
+    """y[n, 0, 0, c] = scale * sum_hw x[n, h, w, c] for any C, without atomics
+    (Global_Avg_Pool of MBConvBlock, EfficientNet.py:184); y dense [N,1,1,C]."""
+    N, H, W, C = x.shape
+    assert y.shape[0] == N and y.shape[-1] == C and y.is_contiguous()
+    wsp, wss = _ws_arg(ws, se_squeeze_workspace(N, H, W, C), x.device)
+    check(_lib.lib().seg_se_squeeze(ptr(x), pixel_stride(x), ptr(y), N, H, W, C, int(c_valid), float(scale), wsp, wss,
+                                    seg_dtype(x), stream_ptr(stream)), "se_squeeze")
+    return y
+
+
+def se_excite_fwd(x, s, y, c_valid, stream=None):
+    """y = x * s, s dense [N,1,1,C] (tf.math.multiply, EfficientNet.py:194)."""
+    N, H, W, C = x.shape
+    assert s.shape[0] == N and s.shape[-1] == C and s.is_contiguous() and s.dtype == x.dtype
+    check(_lib.lib().seg_se_excite_fwd(ptr(x), pixel_stride(x), ptr(s), ptr(y), pixel_stride(y), N, H, W, C,
+                                       int(c_valid), seg_dtype(x), stream_ptr(stream)), "se_excite")
+    return y
+
+
+def se_excite_bwd(x, s, dy, dx, ds, c_valid, ws=None, stream=None, accumulate=False):
+    """dx (+)= dy * s and ds[n, c] = sum_hw dy * x in one pass (ds dense [N,1,1,C])."""
+    N, H, W, C = x.shape
+    assert ds.shape[0] == N and ds.shape[-1] == C and ds.is_contiguous() and s.is_contiguous()
+    wsp, wss = _ws_arg(ws, int(_lib.lib().seg_se_excite_bwd_workspace(N, H, W, C)), x.device)
+    check(_lib.lib().seg_se_excite_bwd(ptr(x), pixel_stride(x), ptr(s), ptr(dy), pixel_stride(dy), ptr(dx),
+                                       pixel_stride(dx), ptr(ds), N, H, W, C, int(c_valid), 2 if accumulate else 0,
+                                       wsp, wss, seg_dtype(x), stream_ptr(stream)), "se_excite_grad")
+    return dx
+
+
+def spatial_reduce_fits(C, dtype):
+    """seg_spatial_reduce takes at most 256 sixteen-byte channel chunks."""
+    return round8(C) // (4 if dtype == F32 else 8) <= 256
+
+
 def add(a, b, y, stream=None):
     check(_lib.lib().seg_add(ptr(a), ptr(b), ptr(y), y.numel(), seg_dtype(y), stream_ptr(stream)),
           "add")

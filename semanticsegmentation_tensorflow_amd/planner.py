@@ -70,7 +70,7 @@ class PlanMixin:
             return
         users = self._users(p)
         for b in p.nodes:
-            if b.kind != "bn" or id(b.output) in fetched:
+            if b.kind != "bn" or b.act is not None or id(b.output) in fetched:
                 continue
             us = users.get(id(b.output), [])
             if len(us) != 1 or us[0].kind != "conv" or us[0].inputs[0] is not b.output:
@@ -99,7 +99,7 @@ class PlanMixin:
             if id(out) in fetched:
                 continue
             us = users.get(id(out), [])
-            if len(us) != 1 or us[0].kind != "bn" or us[0].inputs[0] is not out:
+            if len(us) != 1 or us[0].kind != "bn" or us[0].act is not None or us[0].inputs[0] is not out:
                 continue
             if id(us[0]) in p.folded:
                 # that BN runs inside a 1x1 conv's operand prologue and its
@@ -117,7 +117,7 @@ class PlanMixin:
             t = c.inputs[0]
             us = users.get(id(t), [])
             b = next((n for n in p.nodes if n.kind == "bn" and n.output is t), None)
-            if b is None or len(us) != 1 or id(t) in fetched:
+            if b is None or b.act is not None or len(us) != 1 or id(t) in fetched:
                 continue
             xb = b.inputs[0]
             if len(users.get(id(xb), [])) == 1 and id(xb) not in fetched:
@@ -151,7 +151,11 @@ class PlanMixin:
             d = ops.dwconv_desc(N, H, W, round8(C), C, R, S, op.attrs["stride"], op.attrs["rate"],
                                 op.attrs["padding"], self.cdt)
             return (N, d.OH, d.OW, C)
-        if t in ("BiasAdd", "Relu", "Dropout", "FusedBatchNorm", "Softmax"):
+        if t in ("BiasAdd", "Relu", "Dropout", "FusedBatchNorm", "Softmax", "Swish", "Sigmoid"):
+            return ins[0]
+        if t == "Mul":
+            if len(ins[0]) != 4 or tuple(ins[1]) != (ins[0][0], 1, 1, ins[0][3]):
+                raise ValueError(f"{op.name}: incompatible shapes {ins[0]} vs {ins[1]}")
             return ins[0]
         if t == "Add":
             if ins[0] != ins[1]:
@@ -422,6 +426,12 @@ class PlanMixin:
                     ws_need = max(ws_need, ops.dwconv_bwd_filter_workspace(n.desc))
             elif n.kind == "bn":
                 ws_need = max(ws_need, 4 * 1024 * 2 * round8(s[3]))
+                if n.act is not None and p.train:
+                    ws_need = max(ws_need, ops.bn_act_bwd_workspace(s[0] * s[1] * s[2], round8(s[3])))
+            elif n.kind in ("se_excite", "GlobalAvgPool"):
+                # per-slice partial sums of the squeeze (wide maps) and of the gate gradient
+                N, H, W, C = shp[id(n.inputs[0])]
+                ws_need = max(ws_need, ops.se_squeeze_workspace(N, H, W, round8(C)))
             elif n.kind == "MaxPool" and p.train and id(n.inputs[0]) in p.needs_grad:
                 # the forward records its switches; MaxPoolGrad reads them, not x
                 xb = buf[id(n.inputs[0])]
@@ -545,7 +555,7 @@ class PlanMixin:
             return
         producer = {id(n.output): n for n in p.nodes if n.kind == "conv"}
         for b in p.nodes:
-            if b.kind != "bn" or id(b) in p.folded or id(b.output) in p.fetched:
+            if b.kind != "bn" or b.act is not None or id(b) in p.folded or id(b.output) in p.fetched:
                 continue
             c = producer.get(id(b.inputs[0]))
             if c is None or id(c) in p.pool_fuse or id(c) in p.bn_out2 or id(c.output) in p.fetched or c.fwd_hwio:

@@ -7,7 +7,7 @@ Compilation (per fetch set and fed shapes):
   * fusion of single-consumer chains into one kernel launch each:
       Conv2D [+BiasAdd] [+Relu] [+Dropout]      -> conv (fused epilogue)
       Conv2DTranspose [+BiasAdd] [+Add]         -> tconv (bias + skip fusion)
-      FusedBatchNorm [+Relu]                    -> bn
+      FusedBatchNorm [+Relu | +Swish]           -> bn
       SoftmaxXent + Mean                        -> xent (loss and dlogits)
     and the lowering of a strided 1x1 Conv2D to a shared Subsample node + the
     same conv at stride 1 (planner._lower_strided_1x1);
@@ -56,6 +56,7 @@ class _Node:
         self.kp = None           # conv: keep_prob of the dropout in its epilogue (tensor or number)
         self.kp_val = None       # conv / Dropout: this step's keep_prob and seed (set by the forward)
         self.seed_val = None
+        self.act = None          # bn / act: "swish" or "sigmoid" (seg_bn_act_*); a bn with one takes no ReLU-BN fusion
         self.__dict__.update(kw)
 
 
@@ -540,8 +541,14 @@ class Session(PlanMixin, ForwardMixin, BackwardMixin, StreamMixin):
                 x, gamma, beta = op.inputs
                 chain = [op]
                 relu = absorb(chain, "Relu") is not None
+                # BatchNorm -> swish (MBConvBlock): one seg_bn_act launch, outside the ReLU BN's fusions
+                act = "swish" if not relu and absorb(chain, "Swish") is not None else None
                 nodes.append(_Node("bn", chain, [x], chain[-1].outputs[0], gamma=gamma, beta=beta, relu=relu,
-                                   eps=op.attrs["epsilon"]))
+                                   eps=op.attrs["epsilon"], act=act))
+            elif t in ("Swish", "Sigmoid"):
+                nodes.append(_Node("act", [op], [op.inputs[0]], y, act=t.lower()))
+            elif t == "Mul":
+                nodes.append(_Node("se_excite", [op], list(op.inputs), y))
             elif t == "SoftmaxXent":
                 logits, labels = op.inputs
                 mean = single_consumer(y, "Mean")

@@ -28,6 +28,8 @@ reset_default_graph = _g.reset_default_graph
 shape = _g.shape
 stack = _g.stack
 add = _g.add
+multiply = _g.multiply
+sigmoid = _g.sigmoid
 concat = _g.concat
 pad = _g.pad
 argmax = _g.argmax
@@ -45,6 +47,8 @@ nn = SimpleNamespace(
     conv2d_transpose=_g.conv2d_transpose,
     bias_add=_g.bias_add,
     relu=_g.relu,
+    swish=_g.swish,
+    sigmoid=_g.sigmoid,
     max_pool=_g.max_pool,
     avg_pool=_g.avg_pool,
     dropout=_g.dropout,
@@ -52,6 +56,7 @@ nn = SimpleNamespace(
     global_avg_pool=_g.global_avg_pool,
     softmax_cross_entropy_with_logits=_g.softmax_cross_entropy_with_logits,
 )
+math = SimpleNamespace(multiply=_g.multiply, add=_g.add, sigmoid=_g.sigmoid)
 layers = SimpleNamespace(batch_normalization=_g.batch_normalization)
 image = SimpleNamespace(resize_bilinear=_g.resize_bilinear)
 train = SimpleNamespace(AdamOptimizer=_g.AdamOptimizer, Saver=_ckpt.Saver,
