@@ -521,6 +521,40 @@ int seg_se_excite_bwd(const void* x, int ldx, const void* s, const void* dy, int
                       void* ds, int N, int H, int W, int C, int c_valid, int flags, void* ws,
                       size_t ws_bytes, int dtype, void* stream);
 
+/* ---- TransNet: LiDAR modulation and weighted fusion --------------------------
+ * (Network/model/FCDenseNet_TransNet.py:70-86: relu((alpha + 1) * lid_feat +
+ * beta) :82-83 and relu(x_img + lamda * fuse) :85; csrc/transnet.hip).  NHWC
+ * with a pixel stride ld* (elements) per operand -- any of them may be a
+ * channel slice of a concat buffer -- C % 8 == 0, f32 / bf16 / f16, fp32
+ * arithmetic rounded once, one pass, no workspace, bit-identical from run to
+ * run.  Channels c_valid .. C-1 of every output are written as exact zeros,
+ * whatever the inputs' (or, accumulating, the output's) padding holds.  The
+ * ReLU mask of the gradients is read from the stored y (TF's ReluGrad: 0
+ * where y == 0).  Refused with nothing written: SEG_EINVAL for a null or
+ * misaligned (16-byte) pointer of an operand that is read, no output at all,
+ * a bad dtype / relu / flags, a non-positive size, ld < C or P * ld >= 2^31
+ * elements; SEG_EALIGN for C % 8, c_valid > C or an ld that is not a whole
+ * number of 16-byte chunks.  Operands must not overlap the outputs. */
+/* y = relu?((alpha + alpha_bias) * f + beta): t = alpha + alpha_bias in fp32,
+ * z = fmaf(t, f, beta). */
+int seg_film_fwd(const void* alpha, int lda, const void* f, int ldf, const void* beta, int ldb, void* y,
+                 int ldy, float alpha_bias, long P, int C, int c_valid, int relu, int dtype, void* stream);
+/* dz = dy * (y > 0) (flags bit 0: the forward had the ReLU; else dz = dy and y
+ * is not read); dalpha = dz * f; df = dz * (alpha + alpha_bias); dbeta = dz.
+ * flags bits 1 / 2 / 3: accumulate into dalpha / df / dbeta.  A NULL output
+ * is skipped, and the operand only it reads (f for dalpha, alpha for df) may
+ * then be NULL too. */
+int seg_film_bwd(const void* dy, int lddy, const void* y, int ldy, const void* alpha, int lda, const void* f,
+                 int ldf, void* dalpha, int ldda, void* df, int lddf, void* dbeta, int lddb, float alpha_bias,
+                 long P, int C, int c_valid, int flags, int dtype, void* stream);
+/* y = relu?(a + lam * b) = relu?(fmaf(lam, b, a)). */
+int seg_axpy_relu_fwd(const void* a, int lda, const void* b, int ldb, void* y, int ldy, float lam, long P,
+                      int C, int c_valid, int relu, int dtype, void* stream);
+/* dz = dy * (y > 0) (flags bit 0); da (+)= dz (bit 1); db (+)= lam * dz (bit 2).
+ * A NULL output is skipped. */
+int seg_axpy_relu_bwd(const void* dy, int lddy, const void* y, int ldy, void* da, int ldda, void* db, int lddb,
+                      float lam, long P, int C, int c_valid, int flags, int dtype, void* stream);
+
 /* ---- elementwise -------------------------------------------------------- */
 /* y = a + b  (tf.add, FCN.py:171), dense, n elements. */
 int seg_add(const void* a, const void* b, void* y, long n, int dtype, void* stream);

@@ -22,7 +22,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libsegkern.so")
 # MFMA / no stores -- garbage results) exist only in this separate library;
 # SEG_DIAG_LIB=1 loads it instead of the product library
 DIAG_LIB_PATH = os.path.join(PKG_DIR, "build_diag", "libsegkern_diag.so")
-SOURCES = ["igemm.hip", "igemm2.hip", "igemm3.hip", "halo.hip", "halo4.hip", "dgrad_s2.hip", "wgrad.hip", "conv.hip", "eltwise.hip", "optim.hip", "smallc.hip", "augment.hip", "dense1x1.hip", "pool.hip", "dwconv.hip", "mbconv.hip"]
+SOURCES = ["igemm.hip", "igemm2.hip", "igemm3.hip", "halo.hip", "halo4.hip", "dgrad_s2.hip", "wgrad.hip", "conv.hip", "eltwise.hip", "optim.hip", "smallc.hip", "augment.hip", "dense1x1.hip", "pool.hip", "dwconv.hip", "mbconv.hip", "transnet.hip"]
 HOST_SOURCES = ["pngdec.cpp", "crc32c.cpp"]
 HIP_HOST_SOURCES = ["timing.cpp"]   # host code against the HIP runtime API (hipcc, no kernels)
 HOST_LIBS = ["-lz"]
@@ -225,6 +225,10 @@ SIGNATURES = {
     "seg_se_excite_fwd": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "seg_se_excite_bwd_workspace": (_Z, [_I, _I, _I, _I]),
     "seg_se_excite_bwd": (_I, [_P, _I, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _Z, _I, _P]),
+    "seg_film_fwd": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _F, _L, _I, _I, _I, _I, _P]),
+    "seg_film_bwd": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _F, _L, _I, _I, _I, _I, _P]),
+    "seg_axpy_relu_fwd": (_I, [_P, _I, _P, _I, _P, _I, _F, _L, _I, _I, _I, _I, _P]),
+    "seg_axpy_relu_bwd": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _F, _L, _I, _I, _I, _I, _P]),
     "seg_add": (_I, [_P, _P, _P, _L, _I, _P]),
     "seg_dropout_fwd": (_I, [_P, _P, _L, _F, ctypes.c_uint64, _I, _P]),
     "seg_dropout_bwd": (_I, [_P, _P, _L, _F, ctypes.c_uint64, _I, _P]),

@@ -179,7 +179,9 @@ class BackwardMixin:
                 g.alias_parts(n)
                 continue
             if n.kind == "xent":
-                g.contribute(n.inputs[0], n.dlogits)
+                # only the heads of the loss being minimised; any other loss of the plan is forward-only
+                if n.in_loss:
+                    g.contribute(n.inputs[0], n.dlogits)
                 continue
             dy = g.grad.get(id(n.output))
             if dy is None:
@@ -585,6 +587,41 @@ class BackwardMixin:
             g.done(dx, acc)
         if id(s) in p.needs_grad:
             g.done(ds, sacc)
+
+    def _ew_dest(self, p, t, g):
+        """(buffer, accumulate-after buffer, accumulate-in-kernel flag) of an
+        elementwise gradient output, or (None, None, False) when t needs none."""
+        if id(t) not in p.needs_grad:
+            return None, None, False
+        return g.kernel_dest(t)
+
+    def _bwd_film(self, p, n, dy, g):
+        # dalpha, df and dbeta in one pass; the ReLU mask from the stored output
+        a, f, b = n.inputs
+        if len({id(a), id(f), id(b)}) != 3:
+            raise NotImplementedError(f"{n.ops[0].name}: one tensor as two operands of the modulation")
+        dsts = [self._ew_dest(p, t, g) for t in (a, f, b)]
+        if all(d[0] is None for d in dsts):
+            return
+        ops.film_bwd(dy, p.buf[id(n.output)] if n.relu else None, p.buf[id(a)], p.buf[id(f)], dsts[0][0], dsts[1][0],
+                     dsts[2][0], p.shapes[id(n.output)][3], n.alpha_bias, n.relu, tuple(d[2] for d in dsts))
+        for dst, acc, _ in dsts:
+            if dst is not None:
+                g.done(dst, acc)
+
+    def _bwd_axpy(self, p, n, dy, g):
+        # x's other readers (the concat) add their share through dest / done or the accumulate flag
+        a, b = n.inputs
+        if a is b:
+            raise NotImplementedError(f"{n.ops[0].name}: x + number * x")
+        dsts = [self._ew_dest(p, t, g) for t in (a, b)]
+        if all(d[0] is None for d in dsts):
+            return
+        ops.axpy_relu_bwd(dy, p.buf[id(n.output)] if n.relu else None, dsts[0][0], dsts[1][0],
+                          p.shapes[id(n.output)][3], n.lam, n.relu, tuple(d[2] for d in dsts))
+        for dst, acc, _ in dsts:
+            if dst is not None:
+                g.done(dst, acc)
 
     def _bwd_Relu(self, p, n, dy, g):
         x = n.inputs[0]

@@ -174,10 +174,30 @@ class ForwardMixin:
             ops.copy_channels(p.buf[id(n.inputs[0])], y)
 
     def _fwd_xent(self, p, n, y, scal, seed):
+        if n.twin is not None:
+            return                          # forward-only, on another head's logits and labels: that launch's sum
         lg = p.buf[id(n.inputs[0])]
         labels = p.buf[id(n.labels)]
+        # a head of Mean(sum_i w_i xent_i): dlogits carry loss_scale * w_i / count
         ops.softmax_xent(lg, labels, n.dlogits, n.loss_sum, n.num_classes, n.valid_hw,
-                         grad_scale=(self.loss_scale if p.train else 1.0) / n.count, ws=self.ws)
+                         grad_scale=(self.loss_scale if p.train else 1.0) * n.weight / n.count, ws=self.ws)
+
+    def _fwd_xent_sum(self, p, n, y, scal, seed):
+        if not n.wanted:
+            return                          # the weighted loss is minimised, not fetched
+        ops.fill(n.total, 0.0)
+        for h in n.heads:
+            ops.axpy(n.total, h.loss_sum, h.weight)
+
+    def _fwd_film(self, p, n, y, scal, seed):
+        # relu?((alpha + alpha_bias) * f + beta) in one launch (TransNet, FCDenseNet_TransNet.py:73-79)
+        a, f, b = (p.buf[id(t)] for t in n.inputs)
+        ops.film_fwd(a, f, b, y, p.shapes[id(n.output)][3], n.alpha_bias, n.relu)
+
+    def _fwd_axpy(self, p, n, y, scal, seed):
+        # relu?(x + lam * c) in one launch (FCDenseNet_TransNet.py:83-84)
+        a, b = (p.buf[id(t)] for t in n.inputs)
+        ops.axpy_relu_fwd(a, b, y, p.shapes[id(n.output)][3], n.lam, n.relu)
 
     def _fwd_ConcatV2(self, p, n, y, scal, seed):
         if id(n) not in p.alias_nodes:      # aliased: the parts already sit in place

@@ -119,7 +119,20 @@ class Tensor:
         return TensorShape(self.shape)
 
     def __add__(self, other):
-        return add(self, other)
+        return add_scalar(self, other) if _is_number(other) else add(self, other)
+
+    def __radd__(self, other):
+        if not _is_number(other):
+            return NotImplemented
+        return add_scalar(self, other)
+
+    def __mul__(self, other):
+        return scalar_mul(other, self) if _is_number(other) else multiply(self, other)
+
+    def __rmul__(self, other):
+        if not _is_number(other):
+            return NotImplemented
+        return scalar_mul(other, self)
 
     def __repr__(self):
         return f"<Tensor {self.name} shape={self.shape} {self.dtype}>"
@@ -274,6 +287,19 @@ def Variable_(initial_value=0, trainable=True, name=None, dtype=None):
 def _np_full(shape, v):
     import numpy as _np
     return _np.broadcast_to(_np.asarray(v, dtype=_np.float32), shape).copy()
+
+
+def _is_number(v):
+    import numbers
+    return isinstance(v, numbers.Real) and not isinstance(v, bool)
+
+
+def add_scalar(x, scalar, name=None):
+    """`tensor + number` (TransNet's `Conv2D_Block(...) + 1`,
+    Network/model/FCDenseNet_TransNet.py:73)."""
+    op = Op("AddScalar", [x], {"scalar": float(scalar)}, name)
+    op.outputs[0].shape = x.shape
+    return op.outputs[0]
 
 
 def zeros_like(t, name=None):
@@ -498,14 +524,23 @@ def sigmoid(x, name=None):
 
 def multiply(x, y, name=None):
     """tf.math.multiply of a feature map [N,H,W,C] with a per-image channel
-    gate [N,1,1,C], in either order (se_excite, EfficientNet.py:194); no other
-    broadcast is on the hot path."""
+    gate [N,1,1,C], in either order (se_excite, EfficientNet.py:194: op Mul),
+    or of two feature maps of one shape (TransNet's `alpha * lid_feat`,
+    FCDenseNet_TransNet.py:78: op MulFull); no other broadcast is on the hot
+    path."""
     def gate(t):
         return t.shape is not None and len(t.shape) == 4 and t.shape[1] == 1 and t.shape[2] == 1
 
     def fmap(t):
         return t.shape is not None and len(t.shape) == 4
 
+    if fmap(x) and fmap(y) and not gate(x) and not gate(y):
+        if x is y or tuple(x.shape) != tuple(y.shape):      # (a square has no kernel: two distinct maps)
+            raise NotImplementedError(f"multiply: only [N,H,W,C] x [N,1,1,C] or two tensors of one shape, got "
+                                      f"{x.shape} and {y.shape}")
+        op = Op("MulFull", [x, y], {}, name)
+        op.outputs[0].shape = x.shape
+        return op.outputs[0]
     if fmap(x) and gate(y):
         a, s = x, y
     elif fmap(y) and gate(x):

@@ -824,6 +824,52 @@ def se_excite_bwd(x, s, dy, dx, ds, c_valid, ws=None, stream=None, accumulate=Fa
     return dx
 
 
+def _ld(t):
+    return 0 if t is None else pixel_stride(t)
+
+
+def film_fwd(alpha, f, beta, y, c_valid, alpha_bias=1.0, relu=True, stream=None):
+    """y = relu?((alpha + alpha_bias) * f + beta), the LiDAR modulation of
+    TransNet (Network/model/FCDenseNet_TransNet.py:82-83) in one pass; every
+    operand may be a channel-slice view.  Padding channels of y: zeros."""
+    C = y.shape[-1]
+    check(_lib.lib().seg_film_fwd(ptr(alpha), _ld(alpha), ptr(f), _ld(f), ptr(beta), _ld(beta), ptr(y), _ld(y),
+                                  float(alpha_bias), y.numel() // C, C, int(c_valid), 1 if relu else 0,
+                                  seg_dtype(y), stream_ptr(stream)), "film")
+    return y
+
+
+def film_bwd(dy, y, alpha, f, dalpha, df, dbeta, c_valid, alpha_bias=1.0, relu=True,
+             accumulate=(False, False, False), stream=None):
+    """Gradient of film_fwd: dz = dy * (y > 0) from the stored y (ReluGrad),
+    dalpha (+)= dz * f, df (+)= dz * (alpha + alpha_bias), dbeta (+)= dz;
+    accumulate: one flag per output; an output given as None is skipped."""
+    C = dy.shape[-1]
+    flags = (1 if relu else 0) | (2 if accumulate[0] else 0) | (4 if accumulate[1] else 0) | (
+        8 if accumulate[2] else 0)
+    check(_lib.lib().seg_film_bwd(ptr(dy), _ld(dy), ptr(y), _ld(y), ptr(alpha), _ld(alpha), ptr(f), _ld(f),
+                                  ptr(dalpha), _ld(dalpha), ptr(df), _ld(df), ptr(dbeta), _ld(dbeta),
+                                  float(alpha_bias), dy.numel() // C, C, int(c_valid), flags, seg_dtype(dy),
+                                  stream_ptr(stream)), "film_grad")
+
+
+def axpy_relu_fwd(a, b, y, c_valid, lam, relu=True, stream=None):
+    """y = relu?(a + lam * b), the fusion of TransNet (FCDenseNet_TransNet.py:85)."""
+    C = y.shape[-1]
+    check(_lib.lib().seg_axpy_relu_fwd(ptr(a), _ld(a), ptr(b), _ld(b), ptr(y), _ld(y), float(lam), y.numel() // C, C,
+                                       int(c_valid), 1 if relu else 0, seg_dtype(y), stream_ptr(stream)), "axpy_relu")
+    return y
+
+
+def axpy_relu_bwd(dy, y, da, db, c_valid, lam, relu=True, accumulate=(False, False), stream=None):
+    """dz = dy * (y > 0); da (+)= dz; db (+)= lam * dz; None outputs are skipped."""
+    C = dy.shape[-1]
+    flags = (1 if relu else 0) | (2 if accumulate[0] else 0) | (4 if accumulate[1] else 0)
+    check(_lib.lib().seg_axpy_relu_bwd(ptr(dy), _ld(dy), ptr(y), _ld(y), ptr(da), _ld(da), ptr(db), _ld(db),
+                                       float(lam), dy.numel() // C, C, int(c_valid), flags, seg_dtype(dy),
+                                       stream_ptr(stream)), "axpy_relu_grad")
+
+
 def spatial_reduce_fits(C, dtype):
     """seg_spatial_reduce takes at most 256 sixteen-byte channel chunks."""
     return round8(C) // (4 if dtype == F32 else 8) <= 256

@@ -151,7 +151,12 @@ class PlanMixin:
             d = ops.dwconv_desc(N, H, W, round8(C), C, R, S, op.attrs["stride"], op.attrs["rate"],
                                 op.attrs["padding"], self.cdt)
             return (N, d.OH, d.OW, C)
-        if t in ("BiasAdd", "Relu", "Dropout", "FusedBatchNorm", "Softmax", "Swish", "Sigmoid"):
+        if t in ("BiasAdd", "Relu", "Dropout", "FusedBatchNorm", "Softmax", "Swish", "Sigmoid", "AddScalar",
+                 "ScalarMul"):
+            return ins[0]
+        if t == "MulFull":
+            if len(ins[0]) != 4 or ins[0] != ins[1]:
+                raise ValueError(f"{op.name}: incompatible shapes {ins[0]} vs {ins[1]}")
             return ins[0]
         if t == "Mul":
             if len(ins[0]) != 4 or tuple(ins[1]) != (ins[0][0], 1, 1, ins[0][3]):
@@ -253,7 +258,8 @@ class PlanMixin:
                 # stride: DeepLab's image-pooling ASPP branch
                 xs = shp[id(prod.inputs[0])]
                 return len(xs) == 4 and xs[1] == 1 and xs[2] == 1
-            return prod.kind in ("conv", "AvgPool", "MaxPool", "bn", "tconv") or (
+            # (axpy: TransNet's output opens the next DenseBlock, FCDenseNet_TransNet.py:147)
+            return prod.kind in ("conv", "AvgPool", "MaxPool", "bn", "tconv", "axpy") or (
                 prod.kind == "ConcatV2" and i not in nested)
 
         for root in reversed(concats):
@@ -333,6 +339,13 @@ class PlanMixin:
                 n.count = N * vh * vw
                 n.num_classes = shp[id(lg)][3]
                 buf[id(y)] = n.loss_sum
+                continue
+            if n.kind == "xent_sum":
+                # the fetched value of a weighted loss: sum_i w_i loss_sum_i (/ count at the fetch)
+                n.total = torch.zeros(1, dtype=torch.float32, device=dev)
+                n.count = n.heads[0].count
+                n.wanted = any(f is y for f in p.fetches)
+                buf[id(y)] = n.total
                 continue
             if n.kind in ("ArgMax",):
                 s = shp[id(y)]
@@ -438,6 +451,7 @@ class PlanMixin:
                 if ops.maxpool_argmax_fits(xb):
                     N, H, W, C = xb.shape
                     p.pool_idx[id(n)] = torch.empty(N * (H // 2) * (W // 2) * C, dtype=torch.uint8, device=dev)
+        self._plan_xent_twins(p)
         self._plan_pool_fusion(p, consumers)
         self._plan_bn_outputs(p, consumers)
         ws_need = max(ws_need, 8192)
@@ -455,6 +469,23 @@ class PlanMixin:
         # gradient buffers / plan for backward
         if p.train:
             self._plan_backward(p)
+
+    def _plan_xent_twins(self, p):
+        """A forward-only loss on the logits and labels of another xent node
+        (the reference's summary `loss` beside `training_loss`,
+        FCDenseNet_TransNet.py:267-271) shares that node's launch: it reads the
+        same loss sum and launches nothing."""
+        xs = [n for n in p.nodes if n.kind == "xent"]
+        for i, n in enumerate(xs):
+            if p.train is None or n.in_loss:
+                continue
+            for j, m in enumerate(xs):
+                if (m is not n and m.twin is None and m.inputs[0] is n.inputs[0] and m.labels is n.labels
+                        and m.valid_hw == n.valid_hw and (m.in_loss or j < i)):
+                    n.twin = m
+                    n.loss_sum = m.loss_sum
+                    p.buf[id(n.output)] = m.loss_sum
+                    break
 
     def _plan_pool_fusion(self, p, consumers):
         """conv_layer -> max_pool (Network/model/FCN.py:56-57, :158-160): a

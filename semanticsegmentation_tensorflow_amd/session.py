@@ -9,6 +9,9 @@ Compilation (per fetch set and fed shapes):
       Conv2DTranspose [+BiasAdd] [+Add]         -> tconv (bias + skip fusion)
       FusedBatchNorm [+Relu | +Swish]           -> bn
       SoftmaxXent + Mean                        -> xent (loss and dlogits)
+      Mean(sum_i w_i SoftmaxXent_i)             -> one xent per head + xent_sum
+      AddScalar -> MulFull -> Add [+Relu]       -> film (TransNet's modulation)
+      Add(x, ScalarMul(lam, c)) [+Relu]         -> axpy (TransNet's fusion)
     and the lowering of a strided 1x1 Conv2D to a shared Subsample node + the
     same conv at stride 1 (planner._lower_strided_1x1);
   * static device buffers (NHWC, channels padded to 8) for every activation,
@@ -53,6 +56,9 @@ class _Node:
         self.fwd_hwio = False    # conv: the forward reads the HWIO packed copy
         self.residual = None     # tconv: the skip tensor added in its epilogue
         self.labels = None       # xent
+        self.weight = 1.0        # xent: w_i of Mean(sum_i w_i xent_i)
+        self.in_loss = True      # xent: a head of the loss being minimised (else forward-only)
+        self.twin = None         # xent, forward-only: the xent node on the same logits / labels whose launch it shares
         self.kp = None           # conv: keep_prob of the dropout in its epilogue (tensor or number)
         self.kp_val = None       # conv / Dropout: this step's keep_prob and seed (set by the forward)
         self.seed_val = None
@@ -468,14 +474,52 @@ class Session(PlanMixin, ForwardMixin, BackwardMixin, StreamMixin):
                     needs_grad.add(id(op.outputs[0]))
         p.needs_grad = needs_grad
 
-        p.nodes = self._lower_strided_1x1(p, self._fuse_nodes(order, consumers, fetched, shp), _Node)
+        nodes = self._fuse_nodes(order, consumers, fetched, shp, p.train.inputs[0] if p.train else None)
+        p.nodes = self._lower_strided_1x1(p, nodes, _Node)
         p.fetched = fetched
         self._fold_bn_prologues(p, fetched)
         self._fold_dropout_grads(p, fetched)
         self._allocate(p, consumers, feeds)
         return p
 
-    def _fuse_nodes(self, order, consumers, fetched, shp):
+    _FILM = "only relu?((x + number) * f + beta) is on the hot path (TransNet's modulation): AddScalar -> " \
+            "multiply of two same-shape maps -> Add [-> Relu], each link with one consumer"
+    _AXPY = "number * tensor is on the hot path only as relu?(x + number * c) (TransNet's fusion), as a weight " \
+            "of a loss term, or as tf.scalar_mul on a gradient"
+    _LOSS = "reduce_mean is only supported on the xent loss: softmax_cross_entropy_with_logits, or a sum of " \
+            "such terms each optionally times a Python number"
+
+    def _loss_heads(self, order, consumers, fetched):
+        """Every Mean of the plan as a loss: mean op id -> [(SoftmaxXent op,
+        weight)], and the ids of the Add / ScalarMul ops between them
+        (Mean(xent + 0.4 * xent + 1.6 * xent), FCDenseNet_TransNet.py:268-271;
+        the sum may be nested Adds, the weights are Python numbers)."""
+        heads, inner = {}, set()
+
+        def walk(t, w, terms):
+            if id(t) in fetched or len(consumers.get(id(t), [])) != 1:
+                raise NotImplementedError(self._LOSS)
+            op = t.op
+            if op.type == "SoftmaxXent":
+                terms.append((op, w))
+            elif op.type == "Add":
+                inner.add(op.id)
+                walk(op.inputs[0], w, terms)
+                walk(op.inputs[1], w, terms)
+            elif op.type == "ScalarMul" and not isinstance(op.attrs["scalar"], G.Tensor):
+                inner.add(op.id)
+                walk(op.attrs["x"], w * float(op.attrs["scalar"]), terms)
+            else:
+                raise NotImplementedError(self._LOSS)
+
+        for op in order:
+            if op.type == "Mean":
+                terms = []
+                walk(op.inputs[0], 1.0, terms)
+                heads[op.id] = terms
+        return heads, inner
+
+    def _fuse_nodes(self, order, consumers, fetched, shp, train_loss=None):
         """Fusion of single-consumer op chains into nodes (one launch each)."""
         def single_consumer(t, type_):
             cs = consumers.get(id(t), [])
@@ -494,7 +538,32 @@ class Session(PlanMixin, ForwardMixin, BackwardMixin, StreamMixin):
             absorbed.add(nxt.id)
             return nxt
 
-        absorbed = set()
+        def sole_input(t, type_):
+            """t's producing op when it is a `type_` op read by nothing else."""
+            if t.op.type == type_ and len(consumers.get(id(t), [])) == 1 and id(t) not in fetched:
+                return t.op
+            return None
+
+        def elementwise_chain(add):
+            """Add as the tail of a film or an axpy chain: (kind, inputs, attrs,
+            the ops before it) or None for a plain tf.add."""
+            for i in (0, 1):
+                m, other = sole_input(add.inputs[i], "MulFull"), add.inputs[1 - i]
+                if m is not None:
+                    for j in (0, 1):
+                        a = sole_input(m.inputs[j], "AddScalar")
+                        if a is not None:
+                            return ("film", [a.inputs[0], m.inputs[1 - j], other],
+                                    {"alpha_bias": a.attrs["scalar"]}, [a, m])
+                sm = sole_input(add.inputs[i], "ScalarMul")
+                if sm is not None and not isinstance(sm.attrs["scalar"], G.Tensor):
+                    return ("axpy", [other, sm.attrs["x"]], {"lam": float(sm.attrs["scalar"])}, [sm])
+            return None
+
+        heads, absorbed = self._loss_heads(order, consumers, fetched)
+        xent_of = {x.id: (order_mean, w) for order_mean, terms in heads.items() for x, w in terms}
+        multi = {}           # mean op id -> its xent nodes (a loss that is not the bare SoftmaxXent -> Mean)
+        chained = set()      # AddScalar / MulFull / ScalarMul ops that a film / axpy node took in
         nodes = []
         for op in order:
             if op.id in absorbed or op.type in ("VariableV2",):
@@ -551,21 +620,58 @@ class Session(PlanMixin, ForwardMixin, BackwardMixin, StreamMixin):
                 nodes.append(_Node("se_excite", [op], list(op.inputs), y))
             elif t == "SoftmaxXent":
                 logits, labels = op.inputs
-                mean = single_consumer(y, "Mean")
-                if mean is None:
+                if op.id not in xent_of:
                     raise NotImplementedError("softmax_cross_entropy_with_logits must feed reduce_mean")
-                absorbed.add(mean.id)
-                nodes.append(_Node("xent", [op, mean], [logits], mean.outputs[0], labels=labels,
-                                   valid_hw=op.attrs["valid_hw"]))
+                mid, w = xent_of[op.id]
+                mean = next(o for o in order if o.id == mid)
+                in_loss = train_loss is None or mean.outputs[0] is train_loss
+                if len(heads[mid]) == 1 and mean.inputs[0] is y:
+                    absorbed.add(mean.id)
+                    nodes.append(_Node("xent", [op, mean], [logits], mean.outputs[0], labels=labels,
+                                       valid_hw=op.attrs["valid_hw"], in_loss=in_loss))
+                else:
+                    # a head of a weighted sum: its own launch; the Mean becomes the xent_sum node
+                    nodes.append(_Node("xent", [op], [logits], y, labels=labels, valid_hw=op.attrs["valid_hw"],
+                                       weight=w, in_loss=in_loss))
+                    multi.setdefault(mid, []).append(nodes[-1])
+            elif t == "Mean":
+                hs = multi[op.id]
+                ref = hs[0]
+                for h in hs[1:]:
+                    if (tuple(shp[id(h.inputs[0])][:3]) != tuple(shp[id(ref.inputs[0])][:3])
+                            or h.valid_hw != ref.valid_hw):
+                        raise ValueError(f"{op.name}: the heads of a weighted loss must share N, H, W and valid_hw")
+                nodes.append(_Node("xent_sum", [op], [], y, heads=hs))
+            elif t in ("AddScalar", "MulFull"):
+                # taken in by the Add at the end of their chain (below), or not supported
+                nxt = single_consumer(y, "MulFull" if t == "AddScalar" else "Add")
+                if nxt is None or (t == "MulFull" and (elementwise_chain(nxt) or ("",))[0] != "film"):
+                    raise NotImplementedError(f"{op.name}: {self._FILM}")
+                if t == "AddScalar" and single_consumer(nxt.outputs[0], "Add") is None:
+                    raise NotImplementedError(f"{op.name}: {self._FILM}")
+            elif t == "ScalarMul":
+                nxt = single_consumer(y, "Add")
+                if isinstance(op.attrs["scalar"], G.Tensor) or nxt is None:
+                    raise NotImplementedError(f"{op.name}: {self._AXPY}")
+            elif t == "Add" and elementwise_chain(op) is not None:
+                kind, ins, attrs, before = elementwise_chain(op)
+                for i in ins:
+                    if i.op.type in ("AddScalar", "MulFull", "ScalarMul"):
+                        raise NotImplementedError(f"{op.name}: {self._FILM if kind == 'film' else self._AXPY}")
+                chain = before + [op]
+                chained.update(o.id for o in before)
+                relu = absorb(chain, "Relu") is not None
+                nodes.append(_Node(kind, chain, ins, chain[-1].outputs[0], relu=relu, **attrs))
             elif t == "Placeholder":
                 nodes.append(_Node("input", [op], [], y))
             elif t in ("MaxPool", "AvgPool", "Pool2D", "Pad", "Add", "Relu", "Dropout", "BiasAdd", "ConcatV2",
                        "ResizeBilinear", "ArgMax", "ExpandDims", "Softmax", "GlobalAvgPool"):
                 nodes.append(_Node(t, [op], list(op.inputs), y))
-            elif t == "Mean":
-                raise NotImplementedError("reduce_mean is only supported on the xent loss")
             else:
                 raise NotImplementedError(f"op {t} is not on the hot path")
+        for op in order:
+            if op.type in ("AddScalar", "MulFull", "ScalarMul") and op.id not in absorbed and op.id not in chained:
+                raise NotImplementedError(f"{op.name}: {self._FILM if op.type != 'ScalarMul' else self._AXPY}")
         return nodes
 
     @property
@@ -809,7 +915,7 @@ class Session(PlanMixin, ForwardMixin, BackwardMixin, StreamMixin):
                 continue
             t = p.buf.get(id(f))
             node = next((n for n in p.nodes if n.output is f), None)
-            if node is not None and node.kind == "xent":
+            if node is not None and node.kind in ("xent", "xent_sum"):
                 out[id(f)] = (t / node.count).reshape(())
             elif f.dtype == G.int64:
                 out[id(f)] = t
